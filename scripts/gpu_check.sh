@@ -17,7 +17,7 @@ echo "tests rc=$rc" > $D/steps.txt
 tail -3 $D/gpu_tests.log
 [ $rc -ne 0 ] && exit $rc
 if [ "$BENCH" = bench ]; then
-  timeout -k 10 400 python -u bench.py > $D/bench.json 2> $D/bench.err
+  timeout -k 10 400 python -u bench.py --full > $D/bench.json 2> $D/bench.err
   rc=$?
   echo "bench rc=$rc" >> $D/steps.txt
   cat $D/bench.json | head -c 600

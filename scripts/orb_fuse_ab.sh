@@ -13,7 +13,7 @@ tail -1 $D/tests.log
 for r in $(seq 1 $R); do
   for v in fused split; do
     if [ $v = split ]; then E="LISLAM_ORB_PAIR_SPLIT=1 LISLAM_TI_SPLIT=1"; else E=""; fi
-    env $E timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 --cpu-budget 2 > $D/${v}_$r.json 2> $D/${v}_$r.err || { tail -20 $D/${v}_$r.err; exit 3; }
+    env $E timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 5 --cpu-budget 2 > $D/${v}_$r.json 2> $D/${v}_$r.err || { tail -20 $D/${v}_$r.err; exit 3; }
     python3 -c "
 import json; d=json.load(open('$D/${v}_$r.json')); k=d['roofline']['kernel_ms_isolated_per_step']; p=d['roofline']['kernel_ms_per_step']
 orb=sum(v for n,v in k.items() if n.startswith('k_orb')); orbp=sum(v for n,v in p.items() if n.startswith('k_orb'))

@@ -97,3 +97,43 @@ def test_bench_world_size_mismatch_fails_loudly():
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "4", "--dry-run"],
                          capture_output=True, text=True, timeout=60, env=env, cwd=root)
     assert out.returncode != 0 and "WORLD_SIZE=2" in out.stderr
+
+
+def _import_bench():
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    if root not in sys.path:
+        sys.path.insert(0, root)
+    import bench
+
+    return bench
+
+
+def test_plain_run_has_no_side_legs_and_full_keeps_them():
+    """Without --full the CPU baseline, sustained and segmented legs are off whatever their options
+    say; with --full they keep their defaults and options."""
+    bench = _import_bench()
+    plain = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2", "--cpu-budget", "5"])
+    assert (plain.full, plain.steps, plain.warmup) == (False, 7, 2)
+    assert plain.cpu_budget == 0 and plain.sustain_s == 0 and plain.segmented == 0 and plain.dump_outputs == ""
+    full = bench.parse_args(["--full", "--dump-outputs", "d"])
+    assert full.full and full.cpu_budget == 24.0 and full.sustain_s == 2.5 and full.segmented == 10 and full.dump_outputs == "d"
+    assert bench.parse_args(["--full", "--cpu-budget", "2"]).cpu_budget == 2
+
+
+def test_dump_outputs_writes_float_arrays_within_the_limit(tmp_path):
+    import numpy as np
+
+    bench = _import_bench()
+    arrays = {"pose": np.arange(14.0).reshape(2, 7), "cloud": np.ones((5, 4), np.float32), "stats": np.arange(8, dtype=np.int32)}
+    bench.dump_outputs(str(tmp_path / "a"), 0, arrays)
+    bench.dump_outputs(str(tmp_path / "a"), 1, arrays)
+    for d in (tmp_path / "a", tmp_path / "a" / "rank1"):
+        assert np.load(d / "pose.npy").dtype == np.float64 and np.load(d / "cloud.npy").dtype == np.float32
+        assert np.load(d / "stats.npy").dtype == np.float64 and list(np.load(d / "stats.npy")) == list(range(8))
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "b"), 0, {"big": np.zeros((bench.DUMP_LIMIT_BYTES // 8) + 1)})
+    s = bench.sample_scans(300)
+    assert len(s) == bench.DUMP_SAMPLE_SCANS and list(s) == list(bench.sample_scans(300)) and list(s) == sorted(set(s))
+    assert list(bench.sample_scans(5)) == [0, 1, 2, 3, 4]

@@ -1,7 +1,7 @@
 """Config 4's sharded path on the GPU: `bench.py --gpus 2 --total-scans T` starts two ranks
 (they share the box's one GPU round-robin), each runs its contiguous shard with chains restarting
 at the shard boundary (laserOdometry.cpp:130-135 within a shard), and every
-rank's poses, stats and feature counts equal the oracle's chains over the same shard.  The line
+rank's poses, stats and feature counts equal the oracle's chains over the same shard.  The `--full` line
 itself carries the CPU baseline and every rank's pose delta (bench.py's CPU stage runs on every rank
 before it touches the GPU)."""
 import json
@@ -22,7 +22,7 @@ def test_two_ranks_config4_shards_match_oracle(tmp_path, oracle, synth):
     T, L = 14, 4
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--total-scans", str(T),
-                          "--chain", str(L), "--steps", "2", "--warmup", "1", "--cpu-budget", "2", "--cpu-workers", "2",
+                          "--chain", str(L), "--steps", "2", "--warmup", "1", "--full", "--cpu-budget", "2", "--cpu-workers", "2",
                           "--sustain-s", "0", "--workers", "1", "--dump-dir", str(tmp_path)],
                          capture_output=True, text=True, timeout=280, env=env, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
