@@ -40,6 +40,7 @@
  *                                                                      src/scanRegistration.cpp:592-642
  *   lislam_loop_icp           <- loopClosureThread's USE_ICP block     src/intensity_feature_tracker.cpp:217-366
  *   lislam_odom_fuse          <- odomHandler callback                 src/odom_handler_node.cpp:44-132
+ *   lislam_place_*            <- SCManager (Scan Context)             src/Scancontext.cpp:126-344
  */
 #ifndef LISLAM_H_
 #define LISLAM_H_
@@ -477,6 +478,46 @@ int lislam_odom_fuser_create(lislam_ctx* ctx, lislam_odom_fuser** out);
 int lislam_odom_fuser_destroy(lislam_odom_fuser* f);
 int lislam_odom_fuse(lislam_odom_fuser* f, const double* aloam, const double* intensity, const int32_t* skip, int32_t n,
                      double* fused);
+
+/* ---- Scan Context place recognition: SCManager (include/Scancontext.h, src/Scancontext.cpp) as a
+ * device-resident database.  Entry k is the k-th cloud added (the reference's polarcontexts_[k]). */
+typedef struct lislam_place lislam_place;
+typedef struct {
+  double lidar_height;        /* LIDAR_HEIGHT (2.0) */
+  double max_radius;          /* PC_MAX_RADIUS (80.0) */
+  double search_ratio;        /* SEARCH_RATIO (0.1) */
+  double dist_thres;          /* SC_DIST_THRES (0.13) */
+  int32_t num_ring;           /* PC_NUM_RING (20), 1..40 */
+  int32_t num_sector;         /* PC_NUM_SECTOR (60), 1..120 */
+  int32_t num_exclude_recent; /* NUM_EXCLUDE_RECENT (50) */
+  int32_t num_candidates;     /* NUM_CANDIDATES_FROM_TREE (10), 1..32 */
+  int32_t tree_making_period; /* TREE_MAKING_PERIOD_ (50) */
+} lislam_place_config;
+/* cfg == NULL: the values above (Scancontext.h:77-96).  capacity = the most entries the database holds. */
+int lislam_place_create(lislam_ctx* ctx, const lislam_place_config* cfg, int32_t capacity, lislam_place** out);
+int lislam_place_destroy(lislam_place* p);
+int lislam_place_size(lislam_place* p, int32_t* n);
+/* makeAndSaveScancontextAndKeys (:237-251) of n_clouds clouds: points = their float (x, y, z,
+ * intensity) quadruples one cloud after the other (host or device memory), counts[n_clouds] (host)
+ * their sizes.  A point with a NaN x or y is skipped (undefined in the reference). */
+int lislam_place_add_clouds(lislam_place* p, const void* points, const int32_t* counts, int32_t n_clouds);
+/* The same for cloud_track of scans [first_scan, first_scan + n_scans) of an extracted batch of the
+ * same context (want_images = 1), read where it lies on the device. */
+int lislam_place_add_batch(lislam_place* p, lislam_batch* b, int32_t first_scan, int32_t n_scans);
+/* detectLoopClosureID (:253-344) as it returned when entry k was the newest and had been called once
+ * per entry before, for k in [first, first + n): loop_id (-1: none), yaw = deg2rad(nn_align * 360 / S),
+ * and its internals min_dist, nn_idx, nn_align (1e7, 0, 0 while k < num_exclude_recent).  Host
+ * arrays of n, each nullable.  The candidates are the exact nearest ring keys, equal distances by
+ * lower index. */
+int lislam_place_detect(lislam_place* p, int32_t first, int32_t n, int32_t* loop_id, float* yaw, double* min_dist,
+                        int32_t* nn_idx, int32_t* nn_align);
+/* distanceBtnScanContext (:126-157) of entries a[k] and b[k] (host arrays): dist, shift (nullable). */
+int lislam_place_distance(lislam_place* p, const int32_t* a, const int32_t* b, int32_t n_pairs, double* dist, int32_t* shift);
+#define LISLAM_PLACE_DESC 0       /* double [R * S], row-major ring x sector */
+#define LISLAM_PLACE_RING_KEY 1   /* float [R] */
+#define LISLAM_PLACE_SECTOR_KEY 2 /* double [S] */
+/* One output of entry index into dst (cap elements); *n = the element count. */
+int lislam_place_download(lislam_place* p, int32_t what, int32_t index, void* dst, int32_t cap, int32_t* n);
 
 /* HIP-event timing of the mapping kernels of a context (recorded on its stream, no host sync
  * while recording).  lislam_map_kernel_times synchronizes, returns the total ms and launch count

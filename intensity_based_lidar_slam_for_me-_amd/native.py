@@ -42,6 +42,8 @@ EXPORTED_SYMBOLS = (
     "lislam_intensity_tracker_step", "lislam_batch_intensity_odometry", "lislam_batch_orb_cascade_info", "lislam_batch_ground", "lislam_ground_extract",
     "lislam_lmap_create", "lislam_lmap_destroy", "lislam_lmap_step", "lislam_lmap_counts", "lislam_lmap_points",
     "lislam_batch_odometry_gated", "lislam_odom_step_gated", "lislam_batch_mapopt", "lislam_batch_mapopt_corner", "lislam_loop_icp", "lislam_odom_fuser_create", "lislam_odom_fuser_destroy", "lislam_odom_fuse",
+    "lislam_place_create", "lislam_place_destroy", "lislam_place_size", "lislam_place_add_clouds", "lislam_place_add_batch",
+    "lislam_place_detect", "lislam_place_distance", "lislam_place_download",
 )
 
 MAP_KERNELS = ("k_knn", "k_fit", "k_lm_eval", "k_lm_step", "map_rebuild", "map_downsample", "k_orb_pyramid",
@@ -50,6 +52,8 @@ MAP_KERNELS = ("k_knn", "k_fit", "k_lm_eval", "k_lm_step", "map_rebuild", "map_d
                "k_orb_roiblur", "k_lm_solve")
 
 MATCH_LINE, MATCH_PLANE = 0, 1
+PLACE_DESC, PLACE_RING_KEY, PLACE_SECTOR_KEY = 0, 1, 2
+PLACE_KERNELS = ("k_sc_describe", "k_sc_finish", "k_sc_detect", "k_sc_distance")
 
 
 class Config(ctypes.Structure):
@@ -95,6 +99,19 @@ class IcpConfig(ctypes.Structure):
                  euclidean_fitness_epsilon=1e-6, fitness_threshold=0.5):
         super().__init__(int(use_crop), crop_size, int(use_downsample), voxel_size, max_correspondence_distance,
                          max_iterations, transformation_epsilon, euclidean_fitness_epsilon, fitness_threshold)
+
+
+class PlaceConfig(ctypes.Structure):
+    """lislam_place_config: SCManager's parameters; defaults = Scancontext.h:77-96."""
+
+    _fields_ = [("lidar_height", ctypes.c_double), ("max_radius", ctypes.c_double), ("search_ratio", ctypes.c_double),
+                ("dist_thres", ctypes.c_double), ("num_ring", _i32), ("num_sector", _i32), ("num_exclude_recent", _i32),
+                ("num_candidates", _i32), ("tree_making_period", _i32)]
+
+    def __init__(self, lidar_height=2.0, max_radius=80.0, search_ratio=0.1, dist_thres=0.13, num_ring=20, num_sector=60,
+                 num_exclude_recent=50, num_candidates=10, tree_making_period=50):
+        super().__init__(lidar_height, max_radius, search_ratio, dist_thres, num_ring, num_sector, num_exclude_recent,
+                         num_candidates, tree_making_period)
 
 
 class Frame(ctypes.Structure):
@@ -194,6 +211,14 @@ def load(path: str = LIB_PATH):
     L.lislam_odom_fuser_create.argtypes = [vp, ctypes.POINTER(vp)]
     L.lislam_odom_fuser_destroy.argtypes = [vp]
     L.lislam_odom_fuse.argtypes = [vp, vp, vp, vp, _i32, vp]
+    L.lislam_place_create.argtypes = [vp, ctypes.POINTER(PlaceConfig), _i32, ctypes.POINTER(vp)]
+    L.lislam_place_destroy.argtypes = [vp]
+    L.lislam_place_size.argtypes = [vp, _i32p]
+    L.lislam_place_add_clouds.argtypes = [vp, vp, vp, _i32]
+    L.lislam_place_add_batch.argtypes = [vp, vp, _i32, _i32]
+    L.lislam_place_detect.argtypes = [vp, _i32, _i32, vp, vp, vp, vp, vp]
+    L.lislam_place_distance.argtypes = [vp, vp, vp, _i32, vp, vp]
+    L.lislam_place_download.argtypes = [vp, _i32, _i32, vp, _i32, _i32p]
     L.lislam_map_set_timing.argtypes = [vp, _i32]
     L.lislam_map_kernel_times.argtypes = [vp, _fp, _i32p]
     for name in EXPORTED_SYMBOLS:
