@@ -41,6 +41,8 @@
  *   lislam_loop_icp           <- loopClosureThread's USE_ICP block     src/intensity_feature_tracker.cpp:217-366
  *   lislam_odom_fuse          <- odomHandler callback                 src/odom_handler_node.cpp:44-132
  *   lislam_place_*            <- SCManager (Scan Context)             src/Scancontext.cpp:126-344
+ *   lislam_pgo_*              <- the gtsam factor graph + updatePoses  src/intensity_feature_tracker.cpp:110-145,
+ *                                                                      :314-381, :395-583
  */
 #ifndef LISLAM_H_
 #define LISLAM_H_
@@ -518,6 +520,70 @@ int lislam_place_distance(lislam_place* p, const int32_t* a, const int32_t* b, i
 #define LISLAM_PLACE_SECTOR_KEY 2 /* double [S] */
 /* One output of entry index into dst (cap elements); *n = the element count. */
 int lislam_place_download(lislam_place* p, int32_t what, int32_t index, void* dst, int32_t cap, int32_t* n);
+
+/* ---- Pose-graph optimization: the factor graph of feature_tracker::mapOdomHandle / loopClosureThread
+ * (src/intensity_feature_tracker.cpp:395-583, :314-381) as a device-resident least-squares problem,
+ * solved in batch (Levenberg-Marquardt; it replaces iSAM2's incremental update with the batch optimum
+ * of the same factors).  All fp64.  A pose is 7 doubles qx qy qz qw tx ty tz (as LISLAM_OUT_POSE); a
+ * tangent vector is [omega(3), v(3)], rotation first (GTSAM's Pose3 order), so variances[6] read as
+ * gtsam::noiseModel::Diagonal::Variances does: rad^2 x 3, m^2 x 3.  Exp / Log are the full SE(3) maps,
+ * the retraction is T <- T Exp(delta).
+ *   between factor (i, j, Z, variances, robust), h = Ti^-1 Tj: e = Log(Z^-1 h) / sigma,
+ *     J_j = D / sigma, J_i = -D Ad(h^-1) / sigma, D = the inverse right Jacobian of SE(3) at e sigma;
+ *   prior (node, P, variances): e = Log(P^-1 T) / sigma, J = D / sigma;
+ *   robust = 1: Cauchy(k = 1), cost log(1 + |e|^2) / 2, IRLS weight 1 / (1 + |e|^2); robust = 0: |e|^2 / 2.
+ * Domain: the relative rotation of every Z^-1 h (and P^-1 T) stays below pi - 0.1; outside it the
+ * result is undefined, as Log itself is.
+ * Outer loop: solve (H + lambda clamp(diag H, 1e-6, 1e32)) delta = -g, accept iff the cost strictly
+ * decreases (lambda <- max(lambda / 10, 1e-12)), else lambda <- 10 lambda; stop when an accepted step's
+ * relative cost decrease is below rel_cost_tol, lambda > 1e10 or after max_iterations solves.  The
+ * linear solve is CG preconditioned by the block-tridiagonal part of the damped matrix. */
+typedef struct lislam_pgo lislam_pgo;
+typedef struct {
+  int32_t max_iterations;    /* LM iterations (50) */
+  int32_t cg_max_iterations; /* per solve; 0 = 6 L + 8, L = the edges with |i - j| != 1 (0) */
+  double lambda_init;        /* (1e-4) */
+  double rel_cost_tol;       /* (1e-10) */
+  double cg_rel_tol;         /* |r| / |g| (1e-12) */
+} lislam_pgo_config;
+#define LISLAM_PGO_CONVERGED 0      /* info[0]: relative cost decrease below rel_cost_tol */
+#define LISLAM_PGO_LAMBDA_LIMIT 1   /* lambda > 1e10 */
+#define LISLAM_PGO_MAX_ITERATIONS 2 /* max_iterations solves done */
+/* cfg == NULL: the values in brackets. */
+int lislam_pgo_create(lislam_ctx* ctx, const lislam_pgo_config* cfg, int32_t node_capacity, int32_t edge_capacity,
+                      lislam_pgo** out);
+int lislam_pgo_destroy(lislam_pgo* p);
+int lislam_pgo_size(lislam_pgo* p, int32_t* nodes, int32_t* edges);
+/* n nodes with consecutive ids; pose7[n][7] = each node's initial estimate (host). */
+int lislam_pgo_add_nodes(lislam_pgo* p, const double* pose7, int32_t n);
+/* The graph's one prior (PriorFactor<Pose3>, :444-455); a second call replaces it.  linearize and
+ * optimize need it (LISLAM_ERR_STATE without). */
+int lislam_pgo_set_prior(lislam_pgo* p, int32_t node, const double* pose7, const double* var6);
+/* n between factors (host arrays; robust nullable = all 0).  from < to, from > to and repeated pairs
+ * are accepted; from == to, ids out of range and non-positive variances are LISLAM_ERR_ARG and leave
+ * the graph unchanged. */
+int lislam_pgo_add_edges(lislam_pgo* p, const int32_t* from, const int32_t* to, const double* meas7, const double* var6,
+                         const int32_t* robust, int32_t n);
+/* mapOdomHandle's pose_from.between(pose_to) for scans [first_scan, first_scan + n_scans) of a batch
+ * whose odometry has run: each scan's LISLAM_OUT_POSE row, read where it lies on the device, becomes a
+ * node, and every scan but the first gets an edge pose[k-1]^-1 pose[k] from the node before it; the
+ * first one does too when the graph is not empty and first_scan > 0 (the batch then holds its
+ * predecessor's pose).  var6 == NULL: odometryNoise_ (1e-6 x 3, 1e-8, 1e-8, 1e-6). */
+int lislam_pgo_add_batch(lislam_pgo* p, lislam_batch* batch, int32_t first_scan, int32_t n_scans, const double* var6);
+/* Edges [first, first + n) as the graph holds them (host arrays, each nullable). */
+int lislam_pgo_edges(lislam_pgo* p, int32_t first, int32_t n, int32_t* from, int32_t* to, double* meas7, double* var6,
+                     int32_t* robust);
+/* The factors at the current estimate, the prior last (E = edges): residual[E+1][6] (whitened),
+ * J_from[E][36], J_to[E+1][36] (row-major), weight[E+1], cost.  Host arrays, each nullable. */
+int lislam_pgo_linearize(lislam_pgo* p, double* residual, double* J_from, double* J_to, double* weight, double* cost);
+/* info[8] = status (LISLAM_PGO_*), LM iterations, accepted steps, total CG iterations, most CG
+ * iterations in one solve, nodes, edges, 0; stats[4] = initial cost, final cost, final lambda, last CG
+ * relative residual.  The same graph gives the same bytes from run to run. */
+int lislam_pgo_optimize(lislam_pgo* p, int32_t* info, double* stats);
+/* Nodes [first, first + n): pose7[n][7] and pose6d[n][6] = float x, y, z, roll, pitch, yaw, the
+ * PointTypePose that getTransformMatrix (:152-165) turns back into the node's matrix: it builds
+ * RzRyRx(yaw, pitch, roll), so roll is the angle about z and yaw the one about x (|pitch| < pi / 2). */
+int lislam_pgo_poses(lislam_pgo* p, int32_t first, int32_t n, double* pose7, float* pose6d);
 
 /* HIP-event timing of the mapping kernels of a context (recorded on its stream, no host sync
  * while recording).  lislam_map_kernel_times synchronizes, returns the total ms and launch count

@@ -225,6 +225,10 @@ static int engine_settle(lislam_batch* b) {
     if (rc_ != LISLAM_OK) return rc_;       \
   } while (0)
 
+// engine_settle for the other translation units that read a batch's odometry outputs on the device
+// (lislam_pgo.hip).
+int lislam_batch_settle(lislam_batch* b) { return engine_settle(b); }
+
 int lislam_batch_create(lislam_ctx* c, int32_t max_scans, lislam_batch** out) {
   if (!c || !out || max_scans < 1) return LISLAM_ERR_ARG;
   hipSetDevice(c->device);

@@ -100,6 +100,9 @@ struct lislam_odom {
 };
 
 
+// engine_settle (lislam_abi.cpp) for the other translation units that read a batch's odometry outputs
+// on the device: the context stream waits for a pending engine launch, an aborted one is re-run.
+extern "C" int lislam_batch_settle(lislam_batch* b);
 // Frees lislam_batch::ground / returns the device source of a ground output (lislam_ground.hip).
 void lislam_free_ground(void* p);
 int lislam_ground_batch_output(lislam_batch* b, int what, int scan, const void** src, int* cnt, size_t* esz);

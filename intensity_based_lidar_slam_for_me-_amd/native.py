@@ -44,6 +44,9 @@ EXPORTED_SYMBOLS = (
     "lislam_batch_odometry_gated", "lislam_odom_step_gated", "lislam_batch_mapopt", "lislam_batch_mapopt_corner", "lislam_loop_icp", "lislam_odom_fuser_create", "lislam_odom_fuser_destroy", "lislam_odom_fuse",
     "lislam_place_create", "lislam_place_destroy", "lislam_place_size", "lislam_place_add_clouds", "lislam_place_add_batch",
     "lislam_place_detect", "lislam_place_distance", "lislam_place_download",
+    "lislam_pgo_create", "lislam_pgo_destroy", "lislam_pgo_size", "lislam_pgo_add_nodes", "lislam_pgo_set_prior",
+    "lislam_pgo_add_edges", "lislam_pgo_add_batch", "lislam_pgo_edges", "lislam_pgo_linearize", "lislam_pgo_optimize",
+    "lislam_pgo_poses",
 )
 
 MAP_KERNELS = ("k_knn", "k_fit", "k_lm_eval", "k_lm_step", "map_rebuild", "map_downsample", "k_orb_pyramid",
@@ -54,6 +57,9 @@ MAP_KERNELS = ("k_knn", "k_fit", "k_lm_eval", "k_lm_step", "map_rebuild", "map_d
 MATCH_LINE, MATCH_PLANE = 0, 1
 PLACE_DESC, PLACE_RING_KEY, PLACE_SECTOR_KEY = 0, 1, 2
 PLACE_KERNELS = ("k_sc_describe", "k_sc_finish", "k_sc_detect", "k_sc_distance")
+PGO_CONVERGED, PGO_LAMBDA_LIMIT, PGO_MAX_ITERATIONS = 0, 1, 2
+PGO_KERNELS = ("k_pgo_linearize", "k_pgo_assemble", "k_pgo_sum", "k_pgo_factor", "k_pgo_cg", "k_pgo_retract",
+               "k_pgo_add_batch", "k_pgo_pose6d")
 
 
 class Config(ctypes.Structure):
@@ -112,6 +118,16 @@ class PlaceConfig(ctypes.Structure):
                  num_exclude_recent=50, num_candidates=10, tree_making_period=50):
         super().__init__(lidar_height, max_radius, search_ratio, dist_thres, num_ring, num_sector, num_exclude_recent,
                          num_candidates, tree_making_period)
+
+
+class PgoConfig(ctypes.Structure):
+    """lislam_pgo_config: the Levenberg-Marquardt loop and its CG solve (include/lislam.h)."""
+
+    _fields_ = [("max_iterations", _i32), ("cg_max_iterations", _i32), ("lambda_init", ctypes.c_double),
+                ("rel_cost_tol", ctypes.c_double), ("cg_rel_tol", ctypes.c_double)]
+
+    def __init__(self, max_iterations=50, cg_max_iterations=0, lambda_init=1e-4, rel_cost_tol=1e-10, cg_rel_tol=1e-12):
+        super().__init__(max_iterations, cg_max_iterations, lambda_init, rel_cost_tol, cg_rel_tol)
 
 
 class Frame(ctypes.Structure):
@@ -219,6 +235,17 @@ def load(path: str = LIB_PATH):
     L.lislam_place_detect.argtypes = [vp, _i32, _i32, vp, vp, vp, vp, vp]
     L.lislam_place_distance.argtypes = [vp, vp, vp, _i32, vp, vp]
     L.lislam_place_download.argtypes = [vp, _i32, _i32, vp, _i32, _i32p]
+    L.lislam_pgo_create.argtypes = [vp, ctypes.POINTER(PgoConfig), _i32, _i32, ctypes.POINTER(vp)]
+    L.lislam_pgo_destroy.argtypes = [vp]
+    L.lislam_pgo_size.argtypes = [vp, _i32p, _i32p]
+    L.lislam_pgo_add_nodes.argtypes = [vp, vp, _i32]
+    L.lislam_pgo_set_prior.argtypes = [vp, _i32, vp, vp]
+    L.lislam_pgo_add_edges.argtypes = [vp, vp, vp, vp, vp, vp, _i32]
+    L.lislam_pgo_add_batch.argtypes = [vp, vp, _i32, _i32, vp]
+    L.lislam_pgo_edges.argtypes = [vp, _i32, _i32, vp, vp, vp, vp, vp]
+    L.lislam_pgo_linearize.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.lislam_pgo_optimize.argtypes = [vp, vp, vp]
+    L.lislam_pgo_poses.argtypes = [vp, _i32, _i32, vp, vp]
     L.lislam_map_set_timing.argtypes = [vp, _i32]
     L.lislam_map_kernel_times.argtypes = [vp, _fp, _i32p]
     for name in EXPORTED_SYMBOLS:
