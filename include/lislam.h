@@ -228,6 +228,22 @@ int lislam_set_odometry_schedule(lislam_ctx* ctx, int32_t mode);
  * contexts, e.g. bench.py): 3 / 5.  LISLAM_ENGINE_QPW / LISLAM_ENGINE_DEPTH seed a new context's
  * shape. */
 int lislam_set_engine_shape(lislam_ctx* ctx, int32_t queries_per_wave, int32_t depth);
+/* Engine pairing (results are the same).  At depth > 1 the library's engine dispatcher (a host thread per device) may run the
+ * chains of two batches (of different contexts, or of one) as ONE engine launch: while one chain's
+ * role solves a pass, the launch's item workgroups associate the other chain's, so the pair holds
+ * the CUs of one launch and counts as one engine in flight.  Only compatible requests are paired:
+ * one chain each, the same engine shape, scan geometry and iteration limit.
+ * OFF: never.  AUTO (the default; no effect at depth 1): two requests that are ready together, or a
+ * ready one with a partner whose inputs are about to exist (a short bounded hold, only while another
+ * engine runs).  REQUIRE: a lone request is held until a compatible partner is ready, at most for
+ * the engine's wait bound (2 s), then runs alone (tests: deterministic pairs). */
+#define LISLAM_PAIRING_OFF 0
+#define LISLAM_PAIRING_AUTO 1
+#define LISLAM_PAIRING_REQUIRE 2
+int lislam_set_engine_pairing(lislam_ctx* ctx, int32_t mode);
+/* *paired = 1 if the batch's last engine launch was shared with another batch's chain, else 0
+ * (a settling call, see lislam_batch_odometry_status). */
+int lislam_batch_odometry_paired(lislam_batch* b, int32_t* paired);
 /* status = the number of engine launches of the batch that gave up since the previous status call
  * (one of the engine's bounded device waits expired, e.g. when its two launches could not run
  * together).  An aborted launch is recovered, not refused: the next call that reads or replaces the

@@ -658,11 +658,15 @@ static int run_odometry(lislam_batch* b, int n_scans, int chain_len, const doubl
         r.a = o;
         r.ready = b->eng_ready; r.fork = b->eng_fork; r.join_r = b->eng_join_r; r.join_i = b->eng_join_i;
         r.t0 = e0; r.t1 = e1; r.h_abort = b->h_abort; r.done = b->eng_done;
+        r.pairing = c->eng_pairing;
+        r.ctl_words = (size_t)8 + 10 * (size_t)b->max_scans;  // eng_ctl's allocation (alloc_batch)
+        r.paired = r.held = false;
         queued = lislam::submit_odometry_chain_split(&r) > 0;
       } else {
         queued = lislam::launch_odometry_chain_split(o, b->eng_ready, b->eng_fork, b->eng_join_r, b->eng_join_i, e0, e1,
                                                      b->h_abort, b->eng_done) > 0;
       }
+      b->eng_dispatched = queued && o.eng_depth > 1 && lislam::engine_dispatch_enabled();
       if (queued) b->eng_pending = true;
       else b->eng_split = 0;  // no engine streams on this device after all: the single launch below
     }
@@ -722,6 +726,13 @@ int lislam_batch_odometry_abort_code(lislam_batch* b, int32_t* code) {
 int lislam_device_queue_count(int32_t device, int32_t* masked_queues) {
   if (!masked_queues || device < 0) return LISLAM_ERR_ARG;
   *masked_queues = lislam::masked_queue_count(device);
+  return LISLAM_OK;
+}
+
+int lislam_batch_odometry_paired(lislam_batch* b, int32_t* paired) {
+  if (!b || !paired) return LISLAM_ERR_ARG;
+  SETTLE(b);  // the dispatcher has launched the request: its `paired` is final
+  *paired = b->engine_ran && b->eng_split == 1 && b->eng_dispatched && b->eng_req.paired ? 1 : 0;
   return LISLAM_OK;
 }
 
@@ -1143,6 +1154,12 @@ int lislam_set_engine_shape(lislam_ctx* c, int32_t queries_per_wave, int32_t dep
     return LISLAM_ERR_ARG;
   if (queries_per_wave) c->eng_qpw = queries_per_wave;
   if (depth) c->eng_depth = depth;
+  return LISLAM_OK;
+}
+
+int lislam_set_engine_pairing(lislam_ctx* c, int32_t mode) {
+  if (!c || mode < LISLAM_PAIRING_OFF || mode > LISLAM_PAIRING_REQUIRE) return LISLAM_ERR_ARG;
+  c->eng_pairing = mode;
   return LISLAM_OK;
 }
 

@@ -55,6 +55,7 @@ struct lislam_batch {
   // the split launch as queued with the device's engine dispatcher (lislam::submit_odometry_chain_split):
   // its events are recorded when the dispatcher launches it, so every wait on them first waits for that
   lislam::EngineRequest eng_req;
+  bool eng_dispatched = false;  // the last engine launch went through the dispatcher (eng_req.paired is its)
   // Abort recovery.  Every engine launch (split or single) copies its sticky abort word into h_abort
   // (pinned) and records eng_done behind it; eng_check stays set until the next batch call settles
   // it: the host waits for eng_done and, if the engine gave up (a bounded device wait expired), clears

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include <atomic>
+#include <chrono>
 #include <vector>
 
 #include "lislam_device.hpp"
@@ -170,7 +171,17 @@ struct EngineRequest {
   unsigned* h_abort;
   void* plan = nullptr;  // the launch's parameters, fixed when submitted (its environment knobs included)
   std::atomic<int> state{0};  // 0 none, 1 queued, 2 launched
+  // Pairing (lislam_set_engine_pairing): the dispatcher may launch two compatible one-chain requests
+  // of different batches as one engine (k_odom_roles2 / k_odom_items2), one chain's solve beside the
+  // other's association on the same resident item workgroups.  Each request keeps its own events and
+  // abort words; a give-up marks both.
+  int pairing = 0;         // kPairOff / kPairAuto / kPairRequire
+  size_t ctl_words = 0;    // a.eng_ctl's allocation: a paired launch's control words must fit the first batch's
+  bool paired = false;     // out: the launch was shared (valid once state is 2)
+  bool held = false;       // the dispatcher: waiting for a partner since hold_t0
+  std::chrono::steady_clock::time_point hold_t0;
 };
+constexpr int kPairOff = 0, kPairAuto = 1, kPairRequire = 2;
 int submit_odometry_chain_split(EngineRequest* r);
 void wait_engine_launched(EngineRequest* r);
 bool engine_dispatch_enabled();  // LISLAM_ENGINE_DISPATCH (default 1; 0: launch_odometry_chain_split)

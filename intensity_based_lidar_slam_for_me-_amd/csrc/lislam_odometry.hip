@@ -24,6 +24,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cassert>
 #include <chrono>
 #include <condition_variable>
 #include <cstdlib>
@@ -1565,6 +1566,26 @@ struct EngCtl {
   // the device's solve roles per XCD (k_odom_roles), or null: roles taken without regard to XCD
   unsigned* xbusy = nullptr;
   int rgrid = 0;  // k_odom_roles' grid
+  // a paired launch (two batches' chains in one engine): chains [0, C0) are the first batch's,
+  // [C0, C) the second's; the control words are the first batch's.  C0 = C: one batch.
+  int C0 = 0;
+};
+// The batch (its OdomArgs) and the batch's own chain index of a launch's chain g.  The control words
+// (assoc_done, lm_gen, tickets, abort) are indexed by g; everything in batch memory by the pair.
+struct OneBatch {
+  const OdomArgs& a;
+  __device__ __forceinline__ const OdomArgs& of(int g, int, int* c) const { *c = g; return a; }
+};
+struct OdomArgs2 {
+  OdomArgs b[2];
+};
+struct TwoBatches {
+  const OdomArgs2& aa;
+  __device__ __forceinline__ const OdomArgs& of(int g, int C0, int* c) const {  // g wave-uniform
+    const int second = g >= C0 ? 1 : 0;
+    *c = g - (second ? C0 : 0);
+    return aa.b[second];
+  }
 };
 // Word 31 of an item's eng_part row once its records and share of pass ro are written.
 __device__ __forceinline__ uint64_t eng_tag(const EngCtl& ctl, int ro) {
@@ -2520,7 +2541,8 @@ __device__ __forceinline__ bool eng_solve_pass(const OdomArgs& a, const EngCtl& 
 }
 
 // The solve role of chain c (ticket c): every pass of the chain, in order.  false = aborted.
-__device__ __forceinline__ bool eng_solve_role(const OdomArgs& a, const EngCtl& ctl, EngShared& sh, EngLM& lm, int c,
+// c: the chain within its batch (a); g: within the launch (the control words).
+__device__ __forceinline__ bool eng_solve_role(const OdomArgs& a, const EngCtl& ctl, EngShared& sh, EngLM& lm, int c, int g,
                                                bool wave0, unsigned tk) {
   const int lane = lane_id();
   const size_t rec_stride = (size_t)(a.cap_sharp + a.cap_flat) * 9;  // doubles per chain (a.blk)
@@ -2543,7 +2565,7 @@ __device__ __forceinline__ bool eng_solve_role(const OdomArgs& a, const EngCtl& 
     const unsigned ptk = (unsigned)(ro * ctl.C * (ctl.I + 1)) + tk;  // profile slot of the pass (developer builds)
     if (wave0 && lane == 0) {
       eng_prof(ptk, 1, rt_now());
-      sh.flag0 = ieff > 0 ? eng_wait(ctl.assoc_done(c, ro), (unsigned)ieff, ctl.abort_w(), ctl.wait_ticks, 3u, ctl.backoff) : 1;
+      sh.flag0 = ieff > 0 ? eng_wait(ctl.assoc_done(g, ro), (unsigned)ieff, ctl.abort_w(), ctl.wait_ticks, 3u, ctl.backoff) : 1;
       eng_prof(ptk, 1, rt_now());
     }
     __syncthreads();
@@ -2562,7 +2584,7 @@ __device__ __forceinline__ bool eng_solve_role(const OdomArgs& a, const EngCtl& 
 #pragma unroll
       for (int e = 0; e < 7; e++) st_sc1d(st + e, xs[e]);  // the next pass's items start from it
       drain_stores();
-      st_rlx(ctl.lm_gen(c), (unsigned)(ro + 1));
+      st_rlx(ctl.lm_gen(g), (unsigned)(ro + 1));
 #pragma unroll
       for (int e = 0; e < 7; e++) sh.cx[e] = xs[e];
       if (o == 1) {
@@ -2626,24 +2648,27 @@ __device__ __forceinline__ ItemTicket item_ticket(const EngCtl& ctl, unsigned t)
 }
 
 // An association ticket whose pass's x does not exist yet: its waves 1.. prefetch meanwhile.
-__device__ __forceinline__ int eng_wants_prefetch(const OdomArgs& a, const EngCtl& ctl, unsigned t, unsigned total) {
+template <class Args>
+__device__ __forceinline__ int eng_wants_prefetch(const Args& args, const EngCtl& ctl, unsigned t, unsigned total) {
   if (!ctl.prefetch || t < (unsigned)ctl.roles || t >= total) return 0;
   const ItemTicket it = item_ticket(ctl, t);
   if (it.ro == 0) return 0;
-  int k;
-  if (!pair_of(a, it.c, it.ro >> 1, &k) || it.item >= eng_live_items(a, ctl, k)) return 0;
+  int k, c;
+  const OdomArgs& a = args.of(it.c, ctl.C0, &c);
+  if (!pair_of(a, c, it.ro >> 1, &k) || it.item >= eng_live_items(a, ctl, k)) return 0;
   return ld_rlx(ctl.lm_gen(it.c)) < (unsigned)it.ro ? 1 : 0;
 }
 
-// One association item ticket (pass ro, chain c, item): wait for the pass's x, run the item's
-// queries, publish its records and share.  false = aborted.
+// One association item ticket (pass ro, chain it.c of the launch, item): wait for the pass's x, run
+// the item's queries, publish its records and share.  a, cb: the chain's batch and its index there
+// (OneBatch / TwoBatches).  false = aborted.
 template <int kQpw>
 __device__ __forceinline__ bool eng_item_ticket(const OdomArgs& a, const EngCtl& ctl, EngShared& sh, bool wave0, bool lead,
-                                                const ItemTicket& it) {
+                                                const ItemTicket& it, int cb) {
   bool ok = true;
-  const int ro = uni(it.ro), c = uni(it.c), item = uni(it.item);
+  const int ro = uni(it.ro), g = uni(it.c), c = uni(cb), item = uni(it.item);
   const int r = ro >> 1, o = ro & 1;
-  const unsigned ptk = (unsigned)(ro * ctl.C * (ctl.I + 1) + c * (ctl.I + 1) + item);
+  const unsigned ptk = (unsigned)(ro * ctl.C * (ctl.I + 1) + g * (ctl.I + 1) + item);
   if (wave0 && lead) eng_prof(ptk, 0, rt_now());
   int k;
   bool live = pair_of(a, c, r, &k);
@@ -2659,7 +2684,7 @@ __device__ __forceinline__ bool eng_item_ticket(const OdomArgs& a, const EngCtl&
   // done in the common case; then every wave loads what needs no x while the lead waits for x.
   if (wave0) {
     if (lead) {
-      sh.flag0 = (live && o == 1) ? eng_wait(ctl.assoc_done(c, ro - 1), (unsigned)ieff, ctl.abort_w(), ctl.wait_ticks, 1u, ctl.backoff) : true;
+      sh.flag0 = (live && o == 1) ? eng_wait(ctl.assoc_done(g, ro - 1), (unsigned)ieff, ctl.abort_w(), ctl.wait_ticks, 1u, ctl.backoff) : true;
     }
   }
   __syncthreads();
@@ -2682,7 +2707,7 @@ __device__ __forceinline__ bool eng_item_ticket(const OdomArgs& a, const EngCtl&
     if (lead) {
       if (ok && live) {
         eng_prof(ptk, 2, rt_now());  // the item's lead starts its wait for x
-        ok = eng_wait(ctl.lm_gen(c), (unsigned)ro, ctl.abort_w(), ctl.wait_ticks, 2u, ctl.backoff);
+        ok = eng_wait(ctl.lm_gen(g), (unsigned)ro, ctl.abort_w(), ctl.wait_ticks, 2u, ctl.backoff);
         eng_trace(1, ok ? 2u : 99u);
         eng_prof(ptk, 1, rt_now());
       }
@@ -2711,7 +2736,7 @@ __device__ __forceinline__ bool eng_item_ticket(const OdomArgs& a, const EngCtl&
       if (lead) {
         eng_prof(ptk, 7, rt_now() - tp0);
         st_sc1(reinterpret_cast<uint64_t*>(part_row(a, ctl, c, item)) + 31, eng_tag(ctl, ro));  // row complete
-        add_rlx(ctl.assoc_done(c, ro), 1u);
+        add_rlx(ctl.assoc_done(g, ro), 1u);
         eng_trace(1, 4u);
         eng_prof(ptk, 3, rt_now());
       }
@@ -2745,7 +2770,7 @@ __global__ __launch_bounds__(kEngThreads) void k_odom_chain(OdomArgs a, EngCtl c
     if (lead) {
       const unsigned t = add_rlx(ctl.ticket(), 1u);
       sh.ticket = t;
-      sh.pref = eng_wants_prefetch(a, ctl, t, total);
+      sh.pref = eng_wants_prefetch(OneBatch{a}, ctl, t, total);
       eng_trace(0, t);
     }
   }
@@ -2755,15 +2780,16 @@ __global__ __launch_bounds__(kEngThreads) void k_odom_chain(OdomArgs a, EngCtl c
     bool ok = true;
     if (tk < (unsigned)ctl.roles) {
       const int c = uni((int)tk);
-      ok = eng_solve_role(a, ctl, sh, lm, c, wave0, (unsigned)(c * (ctl.I + 1) + ctl.I));
+      ok = eng_solve_role(a, ctl, sh, lm, c, c, wave0, (unsigned)(c * (ctl.I + 1) + ctl.I));
     } else {
-      ok = eng_item_ticket<1>(a, ctl, sh, wave0, lead, item_ticket(ctl, tk));
+      const ItemTicket it = item_ticket(ctl, tk);
+      ok = eng_item_ticket<1>(a, ctl, sh, wave0, lead, it, it.c);
     }
     if (wave0) {
       if (lead) {
         const unsigned t = add_rlx(ctl.ticket(), 1u);
         sh.ticket = t;
-        sh.pref = eng_wants_prefetch(a, ctl, t, total);
+        sh.pref = eng_wants_prefetch(OneBatch{a}, ctl, t, total);
         eng_trace(0, t);
       }
     }
@@ -2821,7 +2847,8 @@ __global__ __launch_bounds__(256) void k_eng_zero(EngCtl ctl, int words) {
     if (i != 3) ctl.w[i] = 0u;
 }
 
-__global__ __launch_bounds__(kEngThreads) void k_odom_roles(OdomArgs a, EngCtl ctl) {
+template <class Args>
+__device__ __forceinline__ void eng_roles_body(const Args& args, const EngCtl& ctl) {
   __shared__ EngShared sh;
   __shared__ EngLM lm;
   __shared__ unsigned held_x;
@@ -2844,7 +2871,12 @@ __global__ __launch_bounds__(kEngThreads) void k_odom_roles(OdomArgs a, EngCtl c
       // One role per XCD while a free one exists (each XCD holds two role CUs): the workgroups of the
       // next launch that land on this XCD — those that exit at once, or the control words' memset —
       // then find its other role CU free instead of queueing behind this chain.  A workgroup takes
-      // the chain only if its XCD held no role; the last to arrive takes it if none of them could.
+      // a chain only if its XCD held no role; the last C to arrive take what is left (C = 1: the
+      // last one; a paired launch's two roles go to two XCDs while two are free).  Every workgroup
+      // arrives once, so the last C arrivals and the earlier claims draw at least C tickets: every
+      // chain is taken once.  With C = 2 the second-to-last arrival draws before the last workgroup
+      // has tried its own XCD, so it may take a chain on a busy XCD that the last one could have
+      // placed on a free one: the placement is best effort, the counts in xbusy stay balanced.
       const unsigned x = xcc_id();
       unsigned* xb = ctl.xbusy + x;
       unsigned t = ~0u;
@@ -2852,8 +2884,8 @@ __global__ __launch_bounds__(kEngThreads) void k_odom_roles(OdomArgs a, EngCtl c
       if (mine) t = add_rlx(ctl.role_ticket(), 1u);
       else (void)add_rlx(xb, ~0u);
       __threadfence();  // the claim is settled before the arrival is counted
-      if (t >= (unsigned)ctl.C && add_rlx(ctl.role_arrive(), 1u) == (unsigned)ctl.rgrid - 1u) {
-        t = add_rlx(ctl.role_ticket(), 1u);  // the last arrival: every other claim is settled
+      if (t >= (unsigned)ctl.C && add_rlx(ctl.role_arrive(), 1u) + (unsigned)ctl.C >= (unsigned)ctl.rgrid) {
+        t = add_rlx(ctl.role_ticket(), 1u);  // among the last C arrivals (C = 1: every other claim is settled)
         if (t < (unsigned)ctl.C && !mine) (void)add_rlx(xb, 1u);
       } else if (t < (unsigned)ctl.C) {
         (void)add_rlx(ctl.role_arrive(), 1u);
@@ -2864,15 +2896,17 @@ __global__ __launch_bounds__(kEngThreads) void k_odom_roles(OdomArgs a, EngCtl c
     }
   }
   __syncthreads();
-  const int c = uni((int)min(sh.ticket, (unsigned)ctl.C));
-  if (c >= ctl.C) return;
+  const int g = uni((int)min(sh.ticket, (unsigned)ctl.C));
+  if (g >= ctl.C) return;
 #if LISLAM_ENG_STAMPS
   if (wave0 && lane_id() == 0) {
     eng_stamp_max(0, ctl, __builtin_amdgcn_s_memrealtime());
     eng_stamp_max(2, ctl, xcc_id() + 1);
   }
 #endif
-  (void)eng_solve_role(a, ctl, sh, lm, c, wave0, (unsigned)(c * (ctl.I + 1) + ctl.I));
+  int c;
+  const OdomArgs& a = args.of(g, ctl.C0, &c);
+  (void)eng_solve_role(a, ctl, sh, lm, c, g, wave0, (unsigned)(g * (ctl.I + 1) + ctl.I));
 #if LISLAM_ENG_STAMPS
   if (wave0 && lane_id() == 0) eng_stamp_max(1, ctl, __builtin_amdgcn_s_memrealtime());
 #endif
@@ -2881,12 +2915,15 @@ __global__ __launch_bounds__(kEngThreads) void k_odom_roles(OdomArgs a, EngCtl c
     (void)add_rlx(ctl.xbusy + held_x, ~0u);
   }
 }
+__global__ __launch_bounds__(kEngThreads) void k_odom_roles(OdomArgs a, EngCtl ctl) { eng_roles_body(OneBatch{a}, ctl); }
+// The paired launch: the roles of two batches' chains (EngCtl::C0).
+__global__ __launch_bounds__(kEngThreads) void k_odom_roles2(OdomArgs2 aa, EngCtl ctl) { eng_roles_body(TwoBatches{aa}, ctl); }
 
 #ifndef LISLAM_ITEM_WPE
 #define LISLAM_ITEM_WPE 4  // waves per SIMD the items are compiled for: 4 = 128 VGPRs
 #endif
-template <int kQpw>
-__device__ __forceinline__ void eng_items_body(const OdomArgs& a, const EngCtl& ctl) {
+template <int kQpw, class Args>
+__device__ __forceinline__ void eng_items_body(const Args& args, const EngCtl& ctl) {
   __shared__ EngShared sh;
   const unsigned total = (unsigned)ctl.C * ctl.I * 2u * ctl.R;
   const bool wave0 = uni((int)(threadIdx.x >> 6)) == 0;
@@ -2903,18 +2940,21 @@ __device__ __forceinline__ void eng_items_body(const OdomArgs& a, const EngCtl& 
     if (lead) {
       const unsigned t = add_rlx(ctl.ticket(), 1u);
       sh.ticket = t;
-      sh.pref = eng_wants_prefetch(a, ctl, t, total);
+      sh.pref = eng_wants_prefetch(args, ctl, t, total);
     }
   }
   __syncthreads();
   unsigned tk = (unsigned)uni((int)sh.ticket);
   while (tk < total) {
-    const bool ok = eng_item_ticket<kQpw>(a, ctl, sh, wave0, lead, item_ticket(ctl, tk));
+    const ItemTicket it = item_ticket(ctl, tk);
+    int c;
+    const OdomArgs& a = args.of(uni(it.c), ctl.C0, &c);
+    const bool ok = eng_item_ticket<kQpw>(a, ctl, sh, wave0, lead, it, c);
     if (wave0) {
       if (lead) {
         const unsigned t = add_rlx(ctl.ticket(), 1u);
         sh.ticket = t;
-        sh.pref = eng_wants_prefetch(a, ctl, t, total);
+        sh.pref = eng_wants_prefetch(args, ctl, t, total);
       }
     }
     __syncthreads();
@@ -2926,7 +2966,13 @@ __device__ __forceinline__ void eng_items_body(const OdomArgs& a, const EngCtl& 
 }
 template <int kQpw>
 __global__ __launch_bounds__(64 * kMaxItemWaves, LISLAM_ITEM_WPE) void k_odom_items(OdomArgs a, EngCtl ctl) {
-  eng_items_body<kQpw>(a, ctl);
+  eng_items_body<kQpw>(OneBatch{a}, ctl);
+}
+// The paired launch: the items of two batches' chains, dealt in (pass, chain, item) order as ever, so
+// a workgroup done with one batch's item of pass p takes the other's while the first one's role solves.
+template <int kQpw>
+__global__ __launch_bounds__(64 * kMaxItemWaves, LISLAM_ITEM_WPE) void k_odom_items2(OdomArgs2 aa, EngCtl ctl) {
+  eng_items_body<kQpw>(TwoBatches{aa}, ctl);
 }
 // One engine at a time (the latency shape: qpw 1, depth 1, 12-wave items): the same items compiled
 // for 3 waves per SIMD (168 VGPRs: no spills, where the 128-VGPR build spills 36 VGPRs and ~180
@@ -2935,7 +2981,7 @@ __global__ __launch_bounds__(64 * kMaxItemWaves, LISLAM_ITEM_WPE) void k_odom_it
 // 10.43k vs 10.20k / 10.10k, r05solo).  LISLAM_ENGINE_SOLO_ITEMS=0: the 128-VGPR build (A/B).
 constexpr int kSoloItemWaves = 12;
 __global__ __launch_bounds__(64 * kSoloItemWaves, 3) void k_odom_items_solo(OdomArgs a, EngCtl ctl) {
-  eng_items_body<1>(a, ctl);
+  eng_items_body<1>(OneBatch{a}, ctl);
 }
 
 static int item_waves(int qpw, int depth);
@@ -2997,7 +3043,7 @@ int launch_odometry_chain(const OdomArgs& a, hipStream_t st) {
   ctl.gen = next_engine_gen();
   ctl.P = engine_part_rows(a.cap_sharp + a.cap_flat);
   ctl.w = a.eng_ctl;
-  ctl.C = a.n_chains;
+  ctl.C = ctl.C0 = a.n_chains;
   ctl.R = min(a.chain_len, a.S - 1);
   ctl.Q = kEngWaves;  // items run in the engine's own workgroups
   ctl.I = engine_items(a.cap_sharp + a.cap_flat);
@@ -3302,14 +3348,18 @@ struct SplitPlan {
   bool solo = false;
   size_t words = 0;
 };
-static SplitPlan split_plan(const OdomArgs& a, int dev) {
+// b2: a second batch whose chains share the launch (a paired launch, pair_compatible); the control
+// words are a's.
+static SplitPlan split_plan(const OdomArgs& a, int dev, const OdomArgs* b2 = nullptr) {
   SplitPlan p;
   EngCtl& ctl = p.ctl;
   ctl.gen = 0;  // numbered when queued on the device (split_enqueue)
   ctl.P = engine_part_rows(a.cap_sharp + a.cap_flat);
   ctl.w = a.eng_ctl;
-  ctl.C = a.n_chains;
+  ctl.C0 = a.n_chains;
+  ctl.C = a.n_chains + (b2 ? b2->n_chains : 0);
   ctl.R = min(a.chain_len, a.S - 1);
+  if (b2) ctl.R = max(ctl.R, min(b2->chain_len, b2->S - 1));  // the shorter chain ends early (pair_of)
   ctl.qpw = a.eng_qpw >= 1 && a.eng_qpw <= 4 ? a.eng_qpw : 1;  // lislam_set_engine_shape
   ctl.Q = item_waves(ctl.qpw, std::max(1, a.eng_depth));
   ctl.I = (a.cap_sharp + a.cap_flat + ctl.qpi() - 1) / ctl.qpi();
@@ -3336,50 +3386,80 @@ static SplitPlan split_plan(const OdomArgs& a, int dev) {
   const int resident = std::max(1, item_cus * per_cu / p.depth);
   const char* cap_env = getenv("LISLAM_ENGINE_WGS");
   const int cap = cap_env ? atoi(cap_env) : std::min(item_cus, resident);
-  p.grid = ctl.C * ctl.I;
+  // A paired launch keeps the grid and the items per (pass, chain) of one batch's launch: it holds
+  // no more CUs, and every chain's sums are those of its unpaired launch.  Its chains' associations
+  // then take turns on the whole grid, one's solve beside the other's association.
+  p.grid = ctl.C0 * ctl.I;
   if (cap > 0) p.grid = min(p.grid, max(cap, 1));
   const char* bud = getenv("LISLAM_ENGINE_BUDGET");
-  ctl.budget = min(kMaxShareItems, bud ? max(1, atoi(bud)) : max(1, p.grid / ctl.C));
+  ctl.budget = min(kMaxShareItems, bud ? max(1, atoi(bud)) : max(1, p.grid / ctl.C0));
   p.words = ((size_t)6 + ctl.C + (size_t)2 * ctl.R * ctl.C + 3) / 4 * 4;  // + assoc_done, role ticket, arrivals
   p.roles_grid = std::max(ctl.C, xccs);
   ctl.rgrid = p.roles_grid;
-  // one role per XCD for single-chain launches (k_odom_roles); LISLAM_ROLE_GATE=0: any XCD
+  // one role per XCD for single-chain and paired launches (k_odom_roles); LISLAM_ROLE_GATE=0: any XCD
   static const bool xgate = !(getenv("LISLAM_ROLE_GATE") && atoi(getenv("LISLAM_ROLE_GATE")) == 0);
   EngineGate* g = engine_gate(dev);
-  ctl.xbusy = xgate && ctl.C == 1 && role_cus_per_xcd() >= 2 && g ? g->xbusy : nullptr;
+  ctl.xbusy = xgate && (ctl.C == 1 || b2) && role_cus_per_xcd() >= 2 && g ? g->xbusy : nullptr;
   return p;
 }
 
 // Queue one launch on a slot's stream pair: the roles stream waits for `ready` and (if given) for
 // `prev`, the items stream forks from it; `mine` is recorded at the end (the slot's busy mark).
+// r2: the request whose chains share the launch (p = split_plan(a, dev, &r2->a)); its own events are
+// recorded and its abort words copied beside the first request's.
 static void split_enqueue(const OdomArgs& a, SplitPlan& p, hipStream_t roles, hipStream_t items, hipEvent_t ready,
                           hipEvent_t prev, hipEvent_t mine, hipEvent_t fork, hipEvent_t join_r, hipEvent_t join_i,
-                          hipEvent_t t0, hipEvent_t t1, unsigned* h_abort, hipEvent_t done) {
+                          hipEvent_t t0, hipEvent_t t1, unsigned* h_abort, hipEvent_t done,
+                          const EngineRequest* r2 = nullptr) {
   EngCtl& ctl = p.ctl;
   ctl.gen = next_engine_gen();
   (void)hipStreamWaitEvent(roles, ready, 0);
+  if (r2) (void)hipStreamWaitEvent(roles, r2->ready, 0);
   if (prev) (void)hipStreamWaitEvent(roles, prev, 0);
   if (t0) (void)hipEventRecord(t0, roles);
+  if (r2 && r2->t0) (void)hipEventRecord(r2->t0, roles);
   // zero the control words of this launch, all but word 3 (the sticky abort)
   hipLaunchKernelGGL(k_eng_zero, dim3(1), dim3(256), 0, roles, ctl, (int)p.words);
   (void)hipEventRecord(fork, roles);
   (void)hipStreamWaitEvent(items, fork, 0);
-  hipLaunchKernelGGL(k_odom_roles, dim3(p.roles_grid), dim3(kEngThreads), 0, roles, a, ctl);
-  if (p.solo) hipLaunchKernelGGL(k_odom_items_solo, dim3(p.grid), dim3(64 * ctl.Q), 0, items, a, ctl);
-  else switch (ctl.qpw) {
-    case 4: hipLaunchKernelGGL(k_odom_items<4>, dim3(p.grid), dim3(64 * ctl.Q), 0, items, a, ctl); break;
-    case 3: hipLaunchKernelGGL(k_odom_items<3>, dim3(p.grid), dim3(64 * ctl.Q), 0, items, a, ctl); break;
-    case 2: hipLaunchKernelGGL(k_odom_items<2>, dim3(p.grid), dim3(64 * ctl.Q), 0, items, a, ctl); break;
-    default: hipLaunchKernelGGL(k_odom_items<1>, dim3(p.grid), dim3(64 * ctl.Q), 0, items, a, ctl); break;
+  if (r2) {
+    OdomArgs2 aa;
+    aa.b[0] = a;
+    aa.b[1] = r2->a;
+    hipLaunchKernelGGL(k_odom_roles2, dim3(p.roles_grid), dim3(kEngThreads), 0, roles, aa, ctl);
+    switch (ctl.qpw) {
+      case 4: hipLaunchKernelGGL(k_odom_items2<4>, dim3(p.grid), dim3(64 * ctl.Q), 0, items, aa, ctl); break;
+      case 3: hipLaunchKernelGGL(k_odom_items2<3>, dim3(p.grid), dim3(64 * ctl.Q), 0, items, aa, ctl); break;
+      case 2: hipLaunchKernelGGL(k_odom_items2<2>, dim3(p.grid), dim3(64 * ctl.Q), 0, items, aa, ctl); break;
+      default: hipLaunchKernelGGL(k_odom_items2<1>, dim3(p.grid), dim3(64 * ctl.Q), 0, items, aa, ctl); break;
+    }
+  } else {
+    hipLaunchKernelGGL(k_odom_roles, dim3(p.roles_grid), dim3(kEngThreads), 0, roles, a, ctl);
+    if (p.solo) hipLaunchKernelGGL(k_odom_items_solo, dim3(p.grid), dim3(64 * ctl.Q), 0, items, a, ctl);
+    else switch (ctl.qpw) {
+      case 4: hipLaunchKernelGGL(k_odom_items<4>, dim3(p.grid), dim3(64 * ctl.Q), 0, items, a, ctl); break;
+      case 3: hipLaunchKernelGGL(k_odom_items<3>, dim3(p.grid), dim3(64 * ctl.Q), 0, items, a, ctl); break;
+      case 2: hipLaunchKernelGGL(k_odom_items<2>, dim3(p.grid), dim3(64 * ctl.Q), 0, items, a, ctl); break;
+      default: hipLaunchKernelGGL(k_odom_items<1>, dim3(p.grid), dim3(64 * ctl.Q), 0, items, a, ctl); break;
+    }
   }
   (void)hipEventRecord(join_r, roles);
   (void)hipEventRecord(join_i, items);
+  if (r2) {
+    (void)hipEventRecord(r2->join_r, roles);
+    (void)hipEventRecord(r2->join_i, items);
+  }
   (void)hipStreamWaitEvent(items, join_r, 0);  // the device's engine ends when both kernels do
   if (t1) (void)hipEventRecord(t1, items);
+  if (r2 && r2->t1) (void)hipEventRecord(r2->t1, items);
   // the launch's error and sticky abort words to the host, and its end, before the slot's next
   // launch can queue behind it
   if (h_abort) (void)hipMemcpyAsync(h_abort, a.eng_ctl + 2, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, items);
   if (done) (void)hipEventRecord(done, items);
+  if (r2) {  // a give-up marks both batches: the launch's abort words are the first batch's
+    if (r2->h_abort) (void)hipMemcpyAsync(r2->h_abort, a.eng_ctl + 2, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, items);
+    if (r2->done) (void)hipEventRecord(r2->done, items);
+  }
   (void)hipEventRecord(mine, items);
 }
 
@@ -3422,11 +3502,35 @@ int launch_odometry_chain_split(const OdomArgs& a, hipEvent_t ready, hipEvent_t 
 // ---- the engine dispatcher: one host thread per device, started by the first submit and joined by
 // release_engine_streams.  Requests are launched in submission order among those whose `ready`
 // event has completed, each on a slot whose last launch has ended (slot_ev), while fewer than the
-// request's depth engines are in flight.  It polls every 20 us while something waits.
+// request's depth engines are in flight.  Two compatible requests go out as one launch (pairing,
+// below).  It polls every 20 us while something waits.
 bool engine_dispatch_enabled() {
   static const bool on = !(getenv("LISLAM_ENGINE_DISPATCH") && atoi(getenv("LISLAM_ENGINE_DISPATCH")) == 0);
   return on;
 }
+
+// Pairing.  Two queued requests share one launch when both allow it and they are compatible: one
+// chain each, the same depth (> 1), item build and waves, the same caps (so the same I and P), H and
+// iteration limit.  Chains of different length are fine (pair_of ends the shorter one early).
+static bool pair_compatible(const EngineRequest* x, const EngineRequest* y) {
+  if (x == y || x->pairing == kPairOff || y->pairing == kPairOff) return false;
+  const OdomArgs &a = x->a, &b = y->a;
+  const SplitPlan &p = *static_cast<const SplitPlan*>(x->plan), &q = *static_cast<const SplitPlan*>(y->plan);
+  return a.n_chains == 1 && b.n_chains == 1 && p.depth > 1 && p.depth == q.depth && !p.solo && !q.solo &&
+         p.ctl.qpw == q.ctl.qpw && p.ctl.Q == q.ctl.Q && a.cap_sharp == b.cap_sharp && a.cap_flat == b.cap_flat &&
+         a.cap_less_sharp == b.cap_less_sharp && a.H == b.H && a.max_iterations == b.max_iterations &&
+         a.eng_ctl != b.eng_ctl;
+}
+// How long (us) a lone ready request is held for a compatible request that is queued but whose
+// inputs do not exist yet, while another engine runs (pairing auto).  0: pair only what is ready
+// together.  The default, 4 ms, is the shortest hold on the plateau of an A/B on the pipelined stream
+// (100 timed steps of 8 contexts: 23.3k scans/s unpaired, 24.1k at 0, 25.1k at 0.3 ms, 27.8k at
+// 1.5 ms, 29.4k at 4 ms, 29.3k at 10 ms, 29.5k at 30 ms: profiles/pair_hold_ab.txt), about a tenth
+// of a pipelined engine launch.  A constant: the A/B's builds set it with -DLISLAM_PAIR_HOLD_US=n.
+#ifndef LISLAM_PAIR_HOLD_US
+#define LISLAM_PAIR_HOLD_US 4000
+#endif
+constexpr long kPairHoldUs = LISLAM_PAIR_HOLD_US;
 
 static void dispatcher_loop(EngineGate* g, int dev) {
   (void)hipSetDevice(dev);
@@ -3437,39 +3541,95 @@ static void dispatcher_loop(EngineGate* g, int dev) {
       g->cv_req.wait(lk);
       continue;
     }
-    EngineRequest* r = nullptr;
-    size_t at = 0;
-    for (size_t i = 0; i < g->q.size(); i++)
-      if (hipEventQuery(g->q[i]->ready) == hipSuccess) { r = g->q[i]; at = i; break; }
+    // a gated launch in flight (a depth-1 context on this device) holds the CUs its grid was
+    // sized for: nothing is dispatched beside it
+    bool gated = false;
+    for (hipEvent_t e : g->ev) gated = gated || (e && hipEventQuery(e) != hipSuccess);
+    bool running[EngineGate::kMaxDepth];
+    int busy = gated ? EngineGate::kMaxDepth : 0;
+    for (int s = 0; s < EngineGate::kMaxDepth; s++) {
+      running[s] = g->slot_used[s] && hipEventQuery(g->slot_ev[s]) != hipSuccess;
+      busy += running[s];
+    }
+    // the first ready request in submission order takes a free slot, with a ready compatible
+    // partner if there is one.  A request held for its partner keeps a free slot to itself
+    // (`reserved`): a later request, which is not its partner, passes it only onto a further free
+    // slot, so the held one never waits for an engine to end on top of its hold.
+    EngineRequest *r = nullptr, *r2 = nullptr;
+    int free_slot = -1, reserved = 0;
+    const auto now = std::chrono::steady_clock::now();
+    for (size_t i = 0; i < g->q.size() && !r; i++) {
+      EngineRequest* x = g->q[i];
+      if (hipEventQuery(x->ready) != hipSuccess) continue;
+      const SplitPlan& px = *static_cast<SplitPlan*>(x->plan);
+      int fs = -1, skip = reserved;
+      for (int s = 0; s < EngineGate::kMaxDepth && s < px.depth && fs < 0; s++)
+        if (!running[s] && skip-- <= 0) fs = s;
+      if (!(busy + reserved < px.depth && fs >= 0 && slot_streams(g, dev, fs))) break;
+      EngineRequest* y = nullptr;
+      bool coming = false;  // a compatible request whose inputs are still being made
+      for (size_t j = 0; j < g->q.size() && !y; j++) {
+        if (!pair_compatible(x, g->q[j])) continue;
+        if (hipEventQuery(g->q[j]->ready) == hipSuccess) y = g->q[j];
+        else coming = true;
+      }
+      if (!y && !g->stop) {
+        // require: until a partner is ready, within the engine's wait bound (ticks of 10 ns);
+        // auto: only while another engine runs and a partner is on its way, for pair_hold_us
+        long bound_us = -1;
+        if (x->pairing == kPairRequire && x->a.n_chains == 1 && px.depth > 1) bound_us = (long)(px.ctl.wait_ticks / 100ull);
+        else if (x->pairing == kPairAuto && coming && busy > 0) bound_us = kPairHoldUs;
+        // the bound runs from the first poll at which the request could have gone out alone and
+        // was kept back; a hold whose condition lapses is forgotten (the next one starts afresh)
+        if (bound_us > 0) {
+          if (!x->held) { x->held = true; x->hold_t0 = now; }
+          if (std::chrono::duration_cast<std::chrono::microseconds>(now - x->hold_t0).count() < bound_us) {
+            reserved++;
+            continue;
+          }
+        } else {
+          x->held = false;
+        }
+      }
+      r = x;
+      r2 = y;
+      free_slot = fs;
+    }
     if (r) {
-      SplitPlan& p = *static_cast<SplitPlan*>(r->plan);
-      // a gated launch in flight (a depth-1 context on this device) holds the CUs its grid was
-      // sized for: nothing is dispatched beside it
-      bool gated = false;
-      for (hipEvent_t e : g->ev) gated = gated || (e && hipEventQuery(e) != hipSuccess);
-      int busy = gated ? EngineGate::kMaxDepth : 0, free_slot = -1;
-      for (int s = 0; s < EngineGate::kMaxDepth; s++) {
-        const bool running = g->slot_used[s] && hipEventQuery(g->slot_ev[s]) != hipSuccess;
-        busy += running;
-        if (!running && free_slot < 0 && s < p.depth) free_slot = s;
+      if (!g->slot_ev[free_slot]) (void)hipEventCreateWithFlags(&g->slot_ev[free_slot], hipEventDisableTiming);
+      if (r2 && r2->ctl_words > r->ctl_words) std::swap(r, r2);  // the control words: the larger allocation
+      SplitPlan pair;
+      if (r2) {
+        pair = split_plan(r->a, dev, &r2->a);
+        // 8 + 4 R control words (R <= the longer batch's S - 1) against the larger allocation's
+        // 8 + 10 S: they fit.  A build without asserts launches the two unpaired and says so.
+        assert(pair.words <= r->ctl_words);
+        if (pair.words > r->ctl_words) {
+          fprintf(stderr, "lislam: a paired launch's %zu control words exceed eng_ctl's %zu: launched unpaired\n",
+                  pair.words, r->ctl_words);
+          r2 = nullptr;
+        }
       }
-      if (busy < p.depth && free_slot >= 0 && slot_streams(g, dev, free_slot)) {
-        if (!g->slot_ev[free_slot]) (void)hipEventCreateWithFlags(&g->slot_ev[free_slot], hipEventDisableTiming);
-        split_enqueue(r->a, p, g->roles[free_slot], g->items[free_slot], r->ready, nullptr, g->slot_ev[free_slot],
-                      r->fork, r->join_r, r->join_i, r->t0, r->t1, r->h_abort, r->done);
-        g->slot_used[free_slot] = true;
+      SplitPlan& p = r2 ? pair : *static_cast<SplitPlan*>(r->plan);
+      split_enqueue(r->a, p, g->roles[free_slot], g->items[free_slot], r->ready, nullptr, g->slot_ev[free_slot],
+                    r->fork, r->join_r, r->join_i, r->t0, r->t1, r->h_abort, r->done, r2);
+      g->slot_used[free_slot] = true;
 #if LISLAM_ENG_STAMPS
-        fprintf(stderr, "dispatch gen %u slot %d at %.3f ms (queued %zu, busy %d)\n", p.ctl.gen, free_slot,
-                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(),
-                g->q.size(), busy);
+      fprintf(stderr, "dispatch gen %u slot %d at %.3f ms (queued %zu, busy %d, paired %d)\n", p.ctl.gen, free_slot,
+              std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(),
+              g->q.size(), busy, r2 ? 1 : 0);
 #endif
-        g->q.erase(g->q.begin() + (long)at);
-        delete static_cast<SplitPlan*>(r->plan);
-        r->plan = nullptr;
-        r->state.store(2);
-        g->cv_launched.notify_all();
-        continue;
+      for (EngineRequest* x : {r, r2}) {
+        if (!x) continue;
+        g->q.erase(std::find(g->q.begin(), g->q.end(), x));
+        delete static_cast<SplitPlan*>(x->plan);
+        x->plan = nullptr;
+        x->paired = r2 != nullptr;
+        x->held = false;
+        x->state.store(2);
       }
+      g->cv_launched.notify_all();
+      continue;
     }
     (void)hipGetLastError();  // hipEventQuery's not-ready status
     lk.unlock();

@@ -61,6 +61,14 @@ class Context:
         nat.check(self.lib.lislam_set_engine_shape(self.h, int(queries_per_wave), int(depth)), self.h,
                   "lislam_set_engine_shape")
 
+    PAIRING_OFF, PAIRING_AUTO, PAIRING_REQUIRE = 0, 1, 2  # lislam_set_engine_pairing
+
+    def set_engine_pairing(self, mode: int):
+        """lislam_set_engine_pairing: whether the library's dispatcher (a host thread) may run this context's chain and
+        another batch's as one engine launch (depth > 1).  PAIRING_AUTO is the default; PAIRING_REQUIRE
+        holds a lone request for a partner (deterministic pairs: tests).  Results are the same."""
+        nat.check(self.lib.lislam_set_engine_pairing(self.h, int(mode)), self.h, "lislam_set_engine_pairing")
+
     def masked_queues(self) -> int:
         """CU-masked streams (hardware queues) the library holds on this context's device
         (lislam_device_queue_count)."""
@@ -245,6 +253,14 @@ class Batch:
         k = ctypes.c_int32(0)
         nat.check(self.ctx.lib.lislam_batch_odometry_engine(self.h, ctypes.byref(k)), self.ctx.h,
                   "lislam_batch_odometry_engine")
+        return int(k.value)
+
+    def odometry_paired(self) -> int:
+        """1 if the batch's last engine launch was shared with another batch's chain
+        (lislam_batch_odometry_paired)."""
+        k = ctypes.c_int32(0)
+        nat.check(self.ctx.lib.lislam_batch_odometry_paired(self.h, ctypes.byref(k)), self.ctx.h,
+                  "lislam_batch_odometry_paired")
         return int(k.value)
 
     def odometry_abort_code(self) -> int:
