@@ -127,6 +127,9 @@ int lislam_odom_step(lislam_odom* od, const lislam_frame* frame, double* para_ou
  * para_q/para_t carry over and the pose accumulates them (:716-717). */
 int lislam_odom_step_gated(lislam_odom* od, const lislam_frame* frame, int32_t use_aloam, double* para_out,
                            double* pose_out, int32_t* stats_out);
+/* lislam_batch_odometry_status for the node: engine launches of its steps that gave up (each was
+ * re-run on the per-round schedule within the step) since the previous call; the call clears it. */
+int lislam_odom_status(lislam_odom* od, int32_t* status);
 
 /* ---------------------------------------------------------------- batch (device resident) */
 int lislam_batch_create(lislam_ctx* ctx, int32_t max_scans, lislam_batch** out);

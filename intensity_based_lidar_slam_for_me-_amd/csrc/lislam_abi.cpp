@@ -1093,6 +1093,11 @@ int lislam_odom_step_gated(lislam_odom* od, const lislam_frame* fr, int32_t use_
   return odom_step(od, fr, use_aloam ? 1 : 0, para_out, pose_out, stats_out);
 }
 
+int lislam_odom_status(lislam_odom* od, int32_t* status) {
+  if (!od || !status) return LISLAM_ERR_ARG;
+  return lislam_batch_odometry_status(od->ctx->single, status);  // the node's pairs run in the context's batch
+}
+
 // ------------------------------------------------------------------------------ functors
 // The context's factor scratch, at least `bytes` (caller holds c->factor_mu).
 static int factor_scratch(lislam_ctx* c, size_t bytes, uint8_t** out) {

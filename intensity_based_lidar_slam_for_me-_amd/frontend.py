@@ -192,6 +192,13 @@ class LaserOdometry:
         nat.check(rc, self.ctx.h, "lislam_odom_step")
         return para, pose, st
 
+    def status(self) -> int:
+        """Engine launches of this node's steps that gave up since the previous call, each re-run on
+        the per-round schedule within its step (lislam_odom_status).  The call clears it."""
+        st = ctypes.c_int32(0)
+        nat.check(self.ctx.lib.lislam_odom_status(self.h, ctypes.byref(st)), self.ctx.h, "lislam_odom_status")
+        return int(st.value)
+
     def close(self):
         if self.h:
             self.ctx.lib.lislam_odom_destroy(self.h)
