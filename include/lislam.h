@@ -162,15 +162,17 @@ int lislam_batch_odometry_gated(lislam_batch* b, int32_t n_scans, int32_t chain_
  * the stream (no host synchronization). */
 int lislam_batch_set_timing(lislam_batch* b, int32_t enable);
 /* Kernels timed by lislam_batch_kernel_times, in this order. */
-#define LISLAM_NUM_KERNELS 7 /* k_scan_front, k_scan_lines, k_scan_compact, k_target_index,
+#define LISLAM_NUM_KERNELS 9 /* k_scan_front, k_scan_lines, k_scan_compact, k_target_index,
                                 k_odom_assoc, k_odom_lm (the latter includes k_odom_init),
                                 k_odom_chain (the persistent engine of few long chains: association
-                                and solve of every round in one launch) */
+                                and solve of every round in one launch), k_odom_to_end and
+                                k_target_index_round (LISLAM_DISTORTION_TO_END: TransformToEnd of the
+                                scans a round solved and the index of their to-end clouds) */
 /* Synchronize, then return, over the calls recorded since the previous read, the average ms
  * per call spent in each kernel (ms_per_call[LISLAM_NUM_KERNELS]) and the launches per call of
  * each kernel (launches_per_call[LISLAM_NUM_KERNELS], may be null); calls[2] (may be null) =
  * extract / odometry calls averaged.  Clears the record.  (LISLAM_NUM_KERNELS was 6 before the
- * chain engine: size the arrays from the macro.) */
+ * chain engine and 7 before lislam_set_distortion: size the arrays from the macro.) */
 int lislam_batch_kernel_times(lislam_batch* b, float* ms_per_call, int32_t* launches_per_call, int32_t* calls);
 
 #define LISLAM_OUT_IMAGE_RANGE 0     /* uint8  [H*W] */
@@ -198,11 +200,19 @@ int lislam_batch_kernel_times(lislam_batch* b, float* ms_per_call, int32_t* laun
                                         cos 15 deg test, -1 < 3 candidates, -2 no model, -3 sampling
                                         beyond the device map), RANSAC iterations, best inliers,
                                         refit inliers */
+/* 22..24: the clouds TransformToEnd leaves (laserOdometry.cpp:176-194, the block :762-790): they exist
+ * only after an odometry call in LISLAM_DISTORTION_TO_END (lislam_set_distortion), for the scans of
+ * that call; otherwise a download returns LISLAM_ERR_STATE with a lislam_last_error text.  Outputs
+ * 3, 8 and 10 stay as extraction left them. */
+#define LISLAM_OUT_CORNER_LAST 22    /* float4 [n]   less-sharp cloud at the scan's end, intensity = int()
+                                        (/laser_cloud_corner_last) */
+#define LISLAM_OUT_SURF_LAST 23      /* float4 [n]   less-flat cloud, likewise (/laser_cloud_surf_last) */
+#define LISLAM_OUT_FULL_RES_END 24   /* float4 [n]   laser cloud, likewise (/velodyne_cloud_3) */
 /* Copy one output of one scan to host memory; cap/n count elements of the listed type.  dst null:
  * only *n is set (the element count). */
 int lislam_batch_download(lislam_batch* b, int32_t what, int32_t scan, void* dst, int32_t cap, int32_t* n);
 /* toROSMsg of a point-cloud output (laser cloud, the four feature clouds, cloud_track, ground,
- * ORB points; scanRegistration.cpp:592-642): cap / n points written into dst in the given
+ * ORB points, the three to-end clouds; scanRegistration.cpp:592-642): cap / n points written into dst in the given
  * PointCloud2 layout (e.g. PCL PointXYZI: point_step 32, x 0, y 4, z 8, intensity 16), packed on
  * the device; bytes outside the four fields are zero.  lislam_batch_upload parses any layout on
  * the device the same way (fromROSMsg). */
@@ -219,6 +229,28 @@ int lislam_batch_download_cloud(lislam_batch* b, int32_t what, int32_t scan, voi
 #define LISLAM_ENGINE_AUTO 1
 #define LISLAM_ENGINE_ON 2
 int lislam_set_odometry_schedule(lislam_ctx* ctx, int32_t mode);
+/* Motion de-skew of the scan-to-scan odometry: the reference's `#define DISTORTION`
+ * (laserOdometry.cpp:82) for lislam_batch_odometry(_gated) and lislam_odom_step(_gated).
+ * OFF (default): DISTORTION 0, s = 1, today's results bit for bit.
+ * QUERIES: the file compiled with DISTORTION 1 as it stands: TransformToStart (:147-172) and every
+ *   LidarEdgeFactor / LidarPlaneFactor (:548-556, :671-679) take s = (intensity - int(intensity)) /
+ *   SCAN_PERIOD of the query point (float subtraction, fp64 division) and interpolate the pose,
+ *   Identity.slerp(s, q_last_curr) and s t_last_curr.  A negative relTime leaves int(intensity) on the
+ *   line below (s near 10, or slightly negative on line 0); that is the reference's behaviour and kept.
+ * TO_END: QUERIES plus the block :762-790, which the reference keeps under `if (0)`, enabled:
+ *   TransformToEnd (:176-194) moves every frame's less-sharp, less-flat and laser clouds to the scan's
+ *   end with the para the frame ends with (a first frame: the identity; a gated-off frame: the carried
+ *   para), so pair k searches scan k - 1's de-skewed clouds.  They are LISLAM_OUT_CORNER_LAST /
+ *   SURF_LAST / FULL_RES_END.  A chain of a batch starts from its first scan as extraction left it (the
+ *   identity para: the same xyz); a scan that ends one chain and starts the next holds the outputs
+ *   of the chain that solved it, and the batch's scan 0 its identity version.
+ * Modes other than OFF run on the per-round launches: LISLAM_ENGINE_AUTO and LISLAM_ENGINE_ON then
+ * resolve to LISLAM_ENGINE_OFF and lislam_batch_odometry_engine reports 0.  As everywhere, the schedule
+ * does not change results; the chain engine itself is DISTORTION 0 only. */
+#define LISLAM_DISTORTION_OFF 0
+#define LISLAM_DISTORTION_QUERIES 1
+#define LISLAM_DISTORTION_TO_END 2
+int lislam_set_distortion(lislam_ctx* ctx, int32_t mode);
 /* The chain engine's shape for this context's launches (results are the same).
  * queries_per_wave: 1 = one association query per wavefront (64-lane searches: the shortest chain,
  * but one engine's association waves fill half of every CU); 2, 3 = that many 64-lane queries one

@@ -512,7 +512,8 @@ int lislam_batch_download_cloud(lislam_batch* b, int32_t what, int32_t scan, voi
     return fail(c, LISLAM_ERR_ARG, "bad point layout");
   const bool cloud4 = what == LISLAM_OUT_LASER_CLOUD || what == LISLAM_OUT_SHARP || what == LISLAM_OUT_LESS_SHARP ||
                       what == LISLAM_OUT_FLAT || what == LISLAM_OUT_LESS_FLAT || what == LISLAM_OUT_CLOUD_TRACK ||
-                      what == LISLAM_OUT_GROUND || what == LISLAM_OUT_ORB_POINTS;
+                      what == LISLAM_OUT_GROUND || what == LISLAM_OUT_ORB_POINTS || what == LISLAM_OUT_CORNER_LAST ||
+                      what == LISLAM_OUT_SURF_LAST || what == LISLAM_OUT_FULL_RES_END;
   if (!cloud4) return fail(c, LISLAM_ERR_ARG, "output %d is not a point cloud", what);
   hipSetDevice(c->device);
   // the device source of the cloud: lislam_batch_download with a null copy (cap 0) gives the count
@@ -576,10 +577,49 @@ int lislam_batch_extract(lislam_batch* b, int32_t n_scans) {
   return LISLAM_OK;
 }
 
+// The buffers of lislam_set_distortion's modes, made by the first odometry call that needs them:
+// mode 1 the records' s; mode 2 also the three to-end clouds and a second target index over them.
+static int deskew_buffers(lislam_batch* b, int mode) {
+  lislam::DeskewPlan& p = b->deskew;
+  const OdomArgs& o = b->oa;
+  const size_t S = b->max_scans, N = b->N;
+  int rc = LISLAM_OK;
+  if (!p.d.blk_s) rc |= dalloc(b, &p.d.blk_s, S * (b->cap_sharp + b->cap_flat));
+  if (mode == LISLAM_DISTORTION_TO_END && !p.d.te_less_sharp) {
+    rc |= dalloc(b, &p.d.te_less_sharp, S * b->cap_less_sharp);
+    rc |= dalloc(b, &p.d.te_less_flat, S * N);
+    rc |= dalloc(b, &p.d.te_cloud, S * N);
+    p.te_ls = o.idx_ls;
+    p.te_lf = o.idx_lf;
+    for (lislam::TargetIndex* ti : {&p.te_ls, &p.te_lf}) {
+      rc |= dalloc(b, &ti->chunk, S * ti->nchunk * 2);
+      rc |= dalloc(b, &ti->super, S * ti->nsuper * 2);
+      rc |= dalloc(b, &ti->nn_chunk, S * ti->nchunk * 2);
+      rc |= dalloc(b, &ti->nn_super, S * ti->nsuper * 2);
+      rc |= dalloc(b, &ti->sorted, S * ti->cap);
+      rc |= dalloc(b, &ti->keys, S * 2 * ti->cap);
+    }
+    if (rc != LISLAM_OK) p.d.te_less_sharp = nullptr;  // (the partial allocations go with the batch)
+  }
+  return rc == LISLAM_OK ? LISLAM_OK : LISLAM_ERR_DEVICE;
+}
+
+// node: the call is a lislam_odom step (init_host set): no laser cloud, and in LISLAM_DISTORTION_TO_END
+// the pair's targets are slot 0's to-end clouds, which the previous step left.
 static int run_odometry(lislam_batch* b, int n_scans, int chain_len, const double* init_host,
                         const int32_t* use_aloam = nullptr) {
   SETTLE(b);
   lislam_ctx* c = b->ctx;
+  const int mode = c->distortion;
+  const bool node = init_host != nullptr;
+  b->te_scans = 0;
+  if (mode != LISLAM_DISTORTION_OFF) {
+    if (deskew_buffers(b, mode) != LISLAM_OK) return LISLAM_ERR_DEVICE;
+    b->deskew.mode = mode;
+    b->deskew.d.cloud = node ? nullptr : b->fa.cloud;
+    b->deskew.d.n_cloud = b->fa.n_cloud;
+    b->deskew.round0_to_end = node;
+  }
   OdomArgs o = b->oa;
   o.gate = nullptr;
   o.S = n_scans;
@@ -626,7 +666,8 @@ static int run_odometry(lislam_batch* b, int n_scans, int chain_len, const doubl
   o.cn = o.n_chains;
   o.eng_qpw = c->eng_qpw;
   o.eng_depth = c->eng_depth;
-  if (lislam::use_chain_engine(o, c->odom_engine)) {
+  // (modes 1 / 2 live in the per-round kernels only: the engine is DISTORTION 0)
+  if (mode == LISLAM_DISTORTION_OFF && lislam::use_chain_engine(o, c->odom_engine)) {
     // few long chains: one persistent launch sequences every round on the device
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (b->eng_split < 0) {  // the engine's streams, once per batch
@@ -686,8 +727,15 @@ static int run_odometry(lislam_batch* b, int n_scans, int chain_len, const doubl
   }
   b->engine_ran = false;
   if (round_streams(b) != LISLAM_OK) return LISLAM_ERR_DEVICE;
-  launch_odometry(o, b->odo_stream, G, b->odo_fork, b->odo_join, ev, &lislam_batch::event_cb, b);
+  if (mode == LISLAM_DISTORTION_TO_END && !node)  // the batch's scan 0 is a first frame (:762-790 under the identity)
+    lislam::launch_to_end_identity(o, b->deskew, 0, c->stream);
+  launch_odometry(o, b->odo_stream, G, b->odo_fork, b->odo_join, ev, &lislam_batch::event_cb, b,
+                  mode != LISLAM_DISTORTION_OFF ? &b->deskew : nullptr);
   HIPCHK(c, hipGetLastError());
+  if (mode == LISLAM_DISTORTION_TO_END) {
+    b->te_scans = n_scans;
+    b->te_full = !node;
+  }
   return LISLAM_OK;
 }
 
@@ -833,6 +881,21 @@ static int output_source(lislam_batch* b, int what, int scan, const void** src_o
       if (what == LISLAM_OUT_PARA) { src = o.para + (size_t)scan * 7; cnt = 7; esz = 8; }
       else if (what == LISLAM_OUT_POSE) { src = o.pose + (size_t)scan * 7; cnt = 7; esz = 8; }
       else { src = o.stats + (size_t)scan * 8; cnt = 8; esz = 4; }
+      break;
+    }
+    case LISLAM_OUT_CORNER_LAST:
+    case LISLAM_OUT_SURF_LAST:
+    case LISLAM_OUT_FULL_RES_END: {
+      const lislam::DeskewArgs& d = b->deskew.d;
+      if (scan >= b->te_scans || (what == LISLAM_OUT_FULL_RES_END && !b->te_full))
+        return fail(c, LISLAM_ERR_STATE, "output %d of scan %d exists only after an odometry call over it in "
+                    "LISLAM_DISTORTION_TO_END (lislam_set_distortion)", what, scan);
+      const int* np = what == LISLAM_OUT_CORNER_LAST ? f.n_feat + scan * 4 + 1
+                    : what == LISLAM_OUT_SURF_LAST ? f.n_feat + scan * 4 + 3 : f.n_cloud + scan;
+      if (devint(np, &cnt) != LISLAM_OK) return LISLAM_ERR_DEVICE;
+      esz = 16;
+      src = what == LISLAM_OUT_CORNER_LAST ? d.te_less_sharp + (size_t)scan * b->cap_less_sharp
+          : what == LISLAM_OUT_SURF_LAST ? d.te_less_flat + scan * N : d.te_cloud + scan * N;
       break;
     }
     case LISLAM_OUT_ORB_T:
@@ -1042,7 +1105,34 @@ static int copy_slot(lislam_batch* b, int from, int to) {
     rc |= cp(ti->nn_super, (size_t)ti->nsuper * 2 * 16);
     rc |= cp(ti->sorted, (size_t)ti->cap * 16);
   }
+  if (b->ctx->distortion == LISLAM_DISTORTION_TO_END && b->deskew.d.te_less_sharp) {
+    // the last frame's clouds at its scan's end and their index: the next step's targets
+    rc |= cp(b->deskew.d.te_less_sharp, (size_t)b->cap_less_sharp * 16);
+    rc |= cp(b->deskew.d.te_less_flat, (size_t)b->N * 16);
+    for (const TargetIndex* ti : {&b->deskew.te_ls, &b->deskew.te_lf}) {
+      rc |= cp(ti->chunk, (size_t)ti->nchunk * 2 * 16);
+      rc |= cp(ti->super, (size_t)ti->nsuper * 2 * 16);
+      rc |= cp(ti->nn_chunk, (size_t)ti->nchunk * 2 * 16);
+      rc |= cp(ti->nn_super, (size_t)ti->nsuper * 2 * 16);
+      rc |= cp(ti->sorted, (size_t)ti->cap * 16);
+    }
+  }
   return rc ? LISLAM_ERR_DEVICE : LISLAM_OK;
+}
+
+// LISLAM_DISTORTION_TO_END for a node frame that no solve ends (the first frame; the last frame when
+// the mode was switched on between steps): the block :762-790 under the identity para, in `slot`.
+static int node_to_end_identity(lislam_batch* b, int slot) {
+  lislam_ctx* c = b->ctx;
+  if (deskew_buffers(b, LISLAM_DISTORTION_TO_END) != LISLAM_OK) return LISLAM_ERR_DEVICE;
+  b->deskew.mode = LISLAM_DISTORTION_TO_END;
+  b->deskew.d.cloud = nullptr;
+  b->deskew.d.n_cloud = b->fa.n_cloud;
+  OdomArgs o = b->oa;
+  o.S = 2;
+  lislam::launch_to_end_identity(o, b->deskew, slot, c->stream);
+  HIPCHK(c, hipGetLastError());
+  return LISLAM_OK;
 }
 
 static int odom_step(lislam_odom* od, const lislam_frame* fr, int use_aloam, double* para_out, double* pose_out,
@@ -1053,11 +1143,17 @@ static int odom_step(lislam_odom* od, const lislam_frame* fr, int use_aloam, dou
   lislam_batch* b = c->single;
   int rc;
   int32_t st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  const bool to_end = c->distortion == LISLAM_DISTORTION_TO_END;
   if (!od->have_last) {  // first frame: initialization only (laserOdometry.cpp:382-389)
     if ((rc = put_frame(b, 0, fr))) return rc;
+    if (to_end && (rc = node_to_end_identity(b, 0))) return rc;  // :762-790 runs on the first frame too
+    od->te_last = to_end;
     od->have_last = true;
   } else {
     if ((rc = put_frame(b, 1, fr))) return rc;
+    // the mode was switched on after the last frame: its clouds as a first frame would have left them
+    if (to_end && !od->te_last && (rc = node_to_end_identity(b, 0))) return rc;
+    od->te_last = to_end;
     b->extracted = 2;
     od->gate[1] = use_aloam != 0;
     if ((rc = run_odometry(b, 2, 1, od->state, use_aloam < 0 ? nullptr : od->gate))) return rc;
@@ -1151,6 +1247,12 @@ int lislam_eval_factors(lislam_ctx* c, int32_t n, const int32_t* kind, const dou
 int lislam_set_odometry_schedule(lislam_ctx* c, int32_t mode) {
   if (!c || mode < LISLAM_ENGINE_OFF || mode > LISLAM_ENGINE_ON) return LISLAM_ERR_ARG;
   c->odom_engine = mode;
+  return LISLAM_OK;
+}
+
+int lislam_set_distortion(lislam_ctx* c, int32_t mode) {
+  if (!c || mode < LISLAM_DISTORTION_OFF || mode > LISLAM_DISTORTION_TO_END) return LISLAM_ERR_ARG;
+  c->distortion = mode;
   return LISLAM_OK;
 }
 

@@ -27,6 +27,12 @@ struct lislam_batch {
   hipEvent_t stage_ev = nullptr;
   bool stage_busy = false;
   bool timing = false;
+  // lislam_set_distortion: the mode 1 / 2 buffers, allocated by the first odometry call that needs
+  // them (a mode-0 batch holds none).  te_scans: scans [0, te_scans) hold outputs 22..24 (the last
+  // odometry call ran in LISLAM_DISTORTION_TO_END), else 0
+  lislam::DeskewPlan deskew{};
+  bool te_full = false;  // te_cloud holds the laser clouds' to-end version (a batch, not the node)
+  int te_scans = 0;
   // per-call event sets recorded on the stream while timing is on; read back (and released)
   // by lislam_batch_kernel_times, so the timed region never blocks on the host.
   std::vector<std::vector<hipEvent_t>> ext_ev;
@@ -98,6 +104,7 @@ struct lislam_odom {
   double state[14] = {0, 0, 0, 1, 0, 0, 0, 0, 0, 0, 1, 0, 0, 0};
   int frames = 0;
   int32_t gate[2] = {1, 1};  // use_aloam of the two scans of a gated step (kept alive for the async copy)
+  bool te_last = false;      // LISLAM_DISTORTION_TO_END: slot 0 holds the last frame's to-end clouds and their index
 };
 
 

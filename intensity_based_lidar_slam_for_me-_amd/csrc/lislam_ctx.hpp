@@ -42,6 +42,7 @@ struct lislam_ctx {
   int odom_engine = LISLAM_ENGINE_AUTO;     // lislam_set_odometry_schedule
   int eng_qpw = 1, eng_depth = 1;           // lislam_set_engine_shape (the latency shape)
   int eng_pairing = LISLAM_PAIRING_AUTO;    // lislam_set_engine_pairing
+  int distortion = LISLAM_DISTORTION_OFF;   // lislam_set_distortion
   // lislam_eval_factors(_raw): one grow-only device buffer for the blocks, the parameters and the
   // outputs, reused across calls; the mutex serializes callers (Ceres evaluates residual blocks
   // from num_threads threads)

@@ -138,6 +138,24 @@ __device__ __forceinline__ void jslerp_identity(double s, const DJet* q, DJet* o
   out[0] = scale1 * q[0]; out[1] = scale1 * q[1]; out[2] = scale1 * q[2]; out[3] = scale0 + scale1 * q[3];
 }
 
+// The value part of jslerp_identity, without jets: TransformToStart's q_point_last
+// (laserOdometry.cpp:159).  acos and sin(theta) depend on q alone (one value per chain); only the
+// two sin(. theta) are per point.
+__device__ __forceinline__ DQ slerp_identity(double s, const double* q) {
+  const double d = q[3], absD = fabs(d);
+  double scale0, scale1;
+  if (absD >= 1.0 - 2.220446049250313e-16) {
+    scale0 = 1.0 - s;
+    scale1 = s;
+  } else {
+    const double theta = acos(absD), sinTheta = sin(theta);
+    scale0 = sin((1.0 - s) * theta) / sinTheta;
+    scale1 = sin(s * theta) / sinTheta;
+  }
+  if (d < 0) scale1 = -scale1;
+  return DQ{scale1 * q[0], scale1 * q[1], scale1 * q[2], scale0 + scale1 * q[3]};
+}
+
 // lp = Identity.slerp(s, q) c + s t, Eigen's _transformVector (uv = 2 q.vec x c; c + w uv + q.vec x uv).
 __device__ __forceinline__ DJ3 jlast_point(const double* q, const double* t, const double* c, double s) {
   DJet qj[4], ql[4];

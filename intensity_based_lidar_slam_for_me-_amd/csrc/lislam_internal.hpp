@@ -112,6 +112,29 @@ struct OdomArgs {
                       // share of the first evaluation
 };
 
+// DISTORTION 1 (lislam_set_distortion, laserOdometry.cpp:82).  What the mode 1 / 2 kernels take
+// beside OdomArgs, as a kernel argument of their own: OdomArgs and the mode-0 kernels stay as they are.
+constexpr double kScanPeriod = 0.1;  // SCAN_PERIOD (laserOdometry.cpp:88)
+struct DeskewArgs {
+  // [n_chains][cap_sharp + cap_flat] beside OdomArgs::blk: the query's intensity - int(intensity) as
+  // the reference's float subtraction gives it; s = that / SCAN_PERIOD in fp64 (:153, :551, :674)
+  float* blk_s;
+  // TransformToEnd (:176-194, the block :762-790): the laser cloud (null: the node API has none) and
+  // the three clouds at the scan's end (LISLAM_OUT_CORNER_LAST / SURF_LAST / FULL_RES_END)
+  const P4* cloud;     // [S][N]
+  const int* n_cloud;  // [S]
+  P4* te_less_sharp;   // [S][cap_less_sharp]
+  P4* te_less_flat;    // [S][N]
+  P4* te_cloud;        // [S][N]
+};
+// One odometry call's distortion mode for launch_odometry (null / mode 0: today's schedule).
+struct DeskewPlan {
+  int mode;                  // LISLAM_DISTORTION_*
+  DeskewArgs d;
+  TargetIndex te_ls, te_lf;  // mode 2: the index of the to-end clouds, built round by round
+  bool round0_to_end;        // mode 2: round 0 searches the to-end clouds too (the node: the previous step's)
+};
+
 // Batched evaluation of the cost functors (lislam_eval_factors).
 struct FactorArgs {
   int n;
@@ -145,7 +168,14 @@ struct OdoTimed {
 // ev (nullable) receives every launch's timing events (from get_event).
 void launch_odometry(const OdomArgs& a, const hipStream_t* streams, int ngroups, hipEvent_t fork,
                      const hipEvent_t* join, std::vector<OdoTimed>* ev, hipEvent_t (*get_event)(void*),
-                     void* ev_owner);
+                     void* ev_owner, const DeskewPlan* deskew = nullptr);
+// deskew (mode 1 / 2): the same rounds with the DISTORTION 1 instantiations of the two kernels
+// (k_odom_assoc16<2, 1>, k_odom_lm2<1>; mode 0 launches <2, 0> and <0>, the kernels as they were); in
+// mode 2 every round ends with k_odom_to_end (kernel id 7) over the scans it solved and the index
+// build of exactly those scans' to-end clouds (k_target_index_round, id 8), the next round's targets.
+// TransformToEnd of one scan under the identity para (a first frame: the batch's scan 0, a node's
+// first frame) and the index of its to-end clouds.
+void launch_to_end_identity(const OdomArgs& a, const DeskewPlan& p, int scan, hipStream_t st);
 // The same schedule as ONE persistent launch (k_odom_chain, lislam_odometry.hip): every round of
 // the a.n_chains chains, association and solve, sequenced on the device.  Returns the grid size.
 int launch_odometry_chain(const OdomArgs& a, hipStream_t st);

@@ -32,6 +32,7 @@
 #include <deque>
 #include <mutex>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "lislam_device.hpp"
@@ -331,6 +332,15 @@ __global__ __launch_bounds__(512, LISLAM_TI_WPE32) void k_target_index_all(OdomA
 __device__ __forceinline__ P4 transform_to_start(const P4& pi, const double* x) {
   const DQ q{x[0], x[1], x[2], x[3]};
   const D3 u = qrot(q, D3{(double)pi.x, (double)pi.y, (double)pi.z}) + D3{1.0 * x[4], 1.0 * x[5], 1.0 * x[6]};
+  return P4{(float)u.x, (float)u.y, (float)u.z, pi.i};
+}
+
+// DISTORTION 1 (:152-153): ds = intensity - int(intensity) in float, s = ds / SCAN_PERIOD in fp64,
+// Identity.slerp(s, q) * p + s t.  A negative relTime leaves int() on the line below (s near 10, or
+// slightly negative on line 0): the reference's behaviour, kept.
+__device__ __forceinline__ float rel_ds(float intensity) { return intensity - (float)int(intensity); }
+__device__ __forceinline__ P4 transform_to_start_s(const P4& pi, const double* x, double s) {
+  const D3 u = qrot(slerp_identity(s, x), D3{(double)pi.x, (double)pi.y, (double)pi.z}) + D3{s * x[4], s * x[5], s * x[6]};
   return P4{(float)u.x, (float)u.y, (float)u.z, pi.i};
 }
 
@@ -990,8 +1000,14 @@ __device__ __forceinline__ void ls16(const P4* L, const float4* chm, int n, int 
   }
 }
 
-template <int kW>
-__global__ __launch_bounds__(64 * kW) void k_odom_assoc16(OdomArgs a, int r, int qblocks) {
+// The distortion mode is a template parameter of the two per-round kernels: kMode 0 = DISTORTION 0
+// (s = 1; its instantiations are the kernels as they were, with an empty last argument), kMode 1 =
+// DISTORTION 1 (s per query point; the last argument is the DeskewArgs).
+template <int kMode> struct DeskewArgsT {};
+template <> struct DeskewArgsT<1> { DeskewArgs v; };
+
+template <int kW, int kMode>
+__global__ __launch_bounds__(64 * kW) void k_odom_assoc16(OdomArgs a, int r, int qblocks, DeskewArgsT<kMode> dw) {
   int c, qb;
   if (a.cn >= 8) {
     const int b = blockIdx.x, x = b & 7, rr = b >> 3;
@@ -1026,7 +1042,14 @@ __global__ __launch_bounds__(64 * kW) void k_odom_assoc16(OdomArgs a, int r, int
   const double* st = a.state + (size_t)c * 16;
   for (int e = 0; e < 7; e++) x[e] = st[e];
   const P4 cur{qp.x, qp.y, qp.z, 0.f};
-  const P4 sel = transform_to_start(cur, x);
+  float ds = 0.f;
+  if constexpr (kMode != 0) {  // the query's own intensity, at its index in the unsorted cloud
+    const P4* src = corner ? a.sharp + (size_t)k * a.cap_sharp : a.flat + (size_t)k * a.cap_flat;
+    if (has) ds = rel_ds(ld4(src + q).i);
+  }
+  P4 sel;
+  if constexpr (kMode != 0) sel = transform_to_start_s(cur, x, (double)ds / kScanPeriod);
+  else sel = transform_to_start(cur, x);
   const int closest = nn16(sorted, nL, ix.nn_chunk + mo, ix.nn_super + so, sel, has);
   const bool act = has && closest >= 0;
   const P4 pa = ld4(L + (act ? closest : 0));
@@ -1053,8 +1076,14 @@ __global__ __launch_bounds__(64 * kW) void k_odom_assoc16(OdomArgs a, int r, int
   const int slot = corner ? q : a.cap_sharp + q;
   double* rec = a.blk + ((size_t)c * (a.cap_sharp + a.cap_flat) + slot) * 9;
   if (found && lr < 9) rec[lr] = v;
-  if (lr == 0) a.blk_kind[(size_t)c * (a.cap_sharp + a.cap_flat) + slot] = found ? (corner ? 0 : 1) : -1;
+  if constexpr (kMode != 0) {  // kinds 5 / 6: the same records with s beside them
+    if (lr == 0) a.blk_kind[(size_t)c * (a.cap_sharp + a.cap_flat) + slot] = found ? (corner ? 5 : 6) : -1;
+    if (found && lr == 9) dw.v.blk_s[(size_t)c * (a.cap_sharp + a.cap_flat) + slot] = ds;
+  } else {
+    if (lr == 0) a.blk_kind[(size_t)c * (a.cap_sharp + a.cap_flat) + slot] = found ? (corner ? 0 : 1) : -1;
+  }
 }
+
 
 // ------------------------------------------------------------------ phase 2: LM solve
 #ifdef LISLAM_PHASE_PROF
@@ -1143,8 +1172,43 @@ __device__ __forceinline__ void block_accum3(int kd, const D3& c, const D3& p1, 
   }
 }
 
-__device__ __forceinline__ void evaluate2(Lm2Shared& sh, const double* blk, const int* kind, int ns, int cap_sharp,
-                                          int nf) {
+// DISTORTION 1: the same records with the query's s (kinds 5 / 6).  The functors interpolate the pose,
+// so the block goes through the 7-slot dual numbers of lislam_factors.hpp (edge_factor_s /
+// plane_factor_s, what ceres::AutoDiffCostFunction evaluates), then the local-parameterization
+// product J_q (R x 4) . d Plus / d delta (4 x 3, EigenQuaternionParameterization::ComputeJacobian),
+// the Huber corrector and the normal-equation sums, as kinds 0 / 1.
+struct Lm2SharedS : Lm2Shared {
+  float ds[kLmLds];  // intensity - int(intensity) of the block's query (s = ds / SCAN_PERIOD)
+};
+__device__ __forceinline__ void block_accum_s(int kd, const double* rec, const double* x, double* acc) {
+  const double ha = 0.1;  // HuberLoss(0.1)
+  DJet rj[3];
+  const int R = kd == 5 ? 3 : 1;
+  if (kd == 5) edge_factor_s(x, x + 4, rec, rj);
+  else plane_factor_s(x, x + 4, rec, rj);
+  double sq = 0;
+  for (int i = 0; i < R; i++) sq += rj[i].a * rj[i].a;
+  const double sc = huber_scale(ha, sq, &acc[0]);
+  // rows k of the plus Jacobian at x = (x, y, z, w)
+  const double P[4][3] = {{x[3], x[2], -x[1]}, {-x[2], x[3], x[0]}, {x[1], -x[0], x[3]}, {-x[0], -x[1], -x[2]}};
+#pragma unroll 1
+  for (int i = 0; i < R; i++) {
+    double Js[6];
+#pragma unroll
+    for (int cc = 0; cc < 3; cc++) {
+      double v = 0;
+#pragma unroll
+      for (int k = 0; k < 4; k++) v += rj[i].v[k] * P[k][cc];
+      Js[cc] = v * sc;
+      Js[3 + cc] = rj[i].v[4 + cc] * sc;
+    }
+    accum_row(acc, Js, rj[i].a * sc);
+  }
+}
+
+template <int kMode, class Shared>
+__device__ __forceinline__ void evaluate2(Shared& sh, const double* blk, const int* kind, int ns, int cap_sharp,
+                                          int nf, const float* blk_s) {
   double acc[kAcc];
 #pragma unroll
   for (int e = 0; e < kAcc; e++) acc[e] = 0;
@@ -1154,11 +1218,13 @@ __device__ __forceinline__ void evaluate2(Lm2Shared& sh, const double* blk, cons
   for (int i = threadIdx.x; i < total; i += kLm2Threads) {
     int kd;
     D3 c, p1, p2;
+    [[maybe_unused]] float ds = 0.f;
     if (i < kLmLds) {
       kd = sh.kind[i];
       c = D3{sh.c[0][i], sh.c[1][i], sh.c[2][i]};
       p1 = D3{sh.p[0][i], sh.p[1][i], sh.p[2][i]};
       p2 = D3{sh.d[0][i], sh.d[1][i], sh.d[2][i]};
+      if constexpr (kMode != 0) ds = sh.ds[i];
     } else {  // beyond the LDS cache
       const int idx = i < ns ? i : cap_sharp + (i - ns);
       kd = kind[idx];
@@ -1166,8 +1232,17 @@ __device__ __forceinline__ void evaluate2(Lm2Shared& sh, const double* blk, cons
       c = D3{rb[0], rb[1], rb[2]};
       p1 = D3{rb[3], rb[4], rb[5]};
       p2 = D3{rb[6], rb[7], rb[8]};
+      if constexpr (kMode != 0) ds = kd >= 0 ? blk_s[idx] : 0.f;
     }
-    if (kd >= 0) block_accum3(kd, c, p1, p2, q, t, acc);
+    if constexpr (kMode != 0) {
+      if (kd >= 0) {
+        const double rec[10] = {c.x, c.y, c.z, p1.x, p1.y, p1.z, p2.x, p2.y, p2.z, (double)ds / kScanPeriod};
+        const double x[7] = {q.x, q.y, q.z, q.w, t.x, t.y, t.z};
+        block_accum_s(kd, rec, x, acc);
+      }
+    } else {
+      if (kd >= 0) block_accum3(kd, c, p1, p2, q, t, acc);
+    }
   }
   const int lane = threadIdx.x & 63, row = threadIdx.x >> 4;
 #pragma unroll
@@ -1187,9 +1262,11 @@ __device__ __forceinline__ void evaluate2(Lm2Shared& sh, const double* blk, cons
   __syncthreads();
 }
 
-__global__ __launch_bounds__(kLm2Threads) void k_odom_lm2(OdomArgs a, int r, int outer) {
-  __shared__ Lm2Shared sh;
+template <int kMode>
+__global__ __launch_bounds__(kLm2Threads) void k_odom_lm2(OdomArgs a, int r, int outer, DeskewArgsT<kMode> dw) {
+  __shared__ std::conditional_t<kMode != 0, Lm2SharedS, Lm2Shared> sh;
   __shared__ LM lm;
+  constexpr int kEdge = kMode != 0 ? 5 : 0, kPlane = kMode != 0 ? 6 : 1;
 #ifdef LISLAM_PHASE_PROF
   unsigned long long t_ph = __builtin_amdgcn_s_memrealtime();
 #endif
@@ -1202,6 +1279,8 @@ __global__ __launch_bounds__(kLm2Threads) void k_odom_lm2(OdomArgs a, int r, int
   const int* kind = a.blk_kind + (size_t)c * (a.cap_sharp + a.cap_flat);
   const bool gated_off = a.gate && !a.gate[k];  // use_aloam false: no solve, the pose still accumulates
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  [[maybe_unused]] const float* blk_s = nullptr;
+  if constexpr (kMode != 0) blk_s = dw.v.blk_s + (size_t)c * (a.cap_sharp + a.cap_flat);
   {
     // the records into LDS, and the correspondence counts (:562/:685)
     int c0 = 0, c1 = 0;
@@ -1209,10 +1288,11 @@ __global__ __launch_bounds__(kLm2Threads) void k_odom_lm2(OdomArgs a, int r, int
     for (int i = threadIdx.x; i < total; i += kLm2Threads) {
       const int idx = i < ns ? i : a.cap_sharp + (i - ns);
       const int kd = kind[idx];
-      c0 += kd == 0;
-      c1 += kd == 1;
+      c0 += kd == kEdge;
+      c1 += kd == kPlane;
       if (i < kLmLds) {
         sh.kind[i] = (int8_t)kd;
+        if constexpr (kMode != 0) sh.ds[i] = kd >= 0 ? blk_s[idx] : 0.f;
         if (kd >= 0) {
           const double* rb = blk + (size_t)idx * 9;
           double v[9];
@@ -1247,7 +1327,7 @@ __global__ __launch_bounds__(kLm2Threads) void k_odom_lm2(OdomArgs a, int r, int
   LM_PHASE(3);
   bool go = (nc + np) > 0;  // no residual blocks: Ceres leaves the parameters untouched
   if (go) {
-    evaluate2(sh, blk, kind, ns, a.cap_sharp, nf);
+    evaluate2<kMode>(sh, blk, kind, ns, a.cap_sharp, nf, blk_s);
     LM_PHASE(0);
     if (threadIdx.x == 0) {
       const bool cont = lm_start(lm, sh.x, sh.acc, a.max_iterations);
@@ -1260,7 +1340,7 @@ __global__ __launch_bounds__(kLm2Threads) void k_odom_lm2(OdomArgs a, int r, int
   }
   LM_PHASE(2);
   while (go) {
-    evaluate2(sh, blk, kind, ns, a.cap_sharp, nf);  // cost + J^T J + J^T r at the candidate
+    evaluate2<kMode>(sh, blk, kind, ns, a.cap_sharp, nf, blk_s);  // cost + J^T J + J^T r at the candidate
     LM_PHASE(1);
 #ifdef LISLAM_PHASE_PROF
     if (threadIdx.x == 0) atomicAdd(&g_lm_phase[5], 1ull);
@@ -1293,6 +1373,62 @@ __global__ __launch_bounds__(kLm2Threads) void k_odom_lm2(OdomArgs a, int r, int
     double* ow = a.pose + (size_t)k * 7;
     for (int e = 0; e < 7; e++) { op[e] = st[e]; ow[e] = st[7 + e]; }
   }
+}
+
+// ------------------------------------------------------------------ TransformToEnd (mode 2)
+// laserOdometry.cpp:176-194 over the less-sharp, less-flat and laser clouds of one scan per chain,
+// the block :762-790: TransformToStart stored to float, then q_last_curr.inverse() * (p - t_last_curr)
+// in fp64 stored to float, intensity = int(intensity).  r >= 0: the scan chain a.c0 + blockIdx.y
+// solved in round r, with the para its second solve left in the chain state (carried where the scan
+// was gated off); r < 0: scan id_scan under the identity para (a first frame: xyz unchanged).
+__global__ __launch_bounds__(256) void k_odom_to_end(OdomArgs a, DeskewArgs d, int r, int id_scan) {
+  int k = id_scan;
+  double x[7] = {0, 0, 0, 1, 0, 0, 0};
+  if (r >= 0) {
+    const int c = a.c0 + blockIdx.y;
+    if (!pair_of(a, c, r, &k)) return;
+    const double* st = a.state + (size_t)c * 16;
+    for (int e = 0; e < 7; e++) x[e] = st[e];
+  }
+  const int n_ls = min(max(a.n_feat[k * 4 + 1], 0), a.cap_less_sharp), n_lf = min(max(a.n_feat[k * 4 + 3], 0), a.N);
+  const int n_cl = d.cloud ? min(max(d.n_cloud[k], 0), a.N) : 0;
+  // Eigen's inverse(): conjugate / squaredNorm (the 4-vector sum in its packet order)
+  const double n2 = (x[0] * x[0] + x[2] * x[2]) + (x[1] * x[1] + x[3] * x[3]);
+  const DQ qi{-x[0] / n2, -x[1] / n2, -x[2] / n2, x[3] / n2};
+  const int total = n_ls + n_lf + n_cl;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
+    const P4* src;
+    P4* dst;
+    if (i < n_ls) {
+      src = a.less_sharp + (size_t)k * a.cap_less_sharp + i;
+      dst = d.te_less_sharp + (size_t)k * a.cap_less_sharp + i;
+    } else if (i < n_ls + n_lf) {
+      src = a.less_flat + (size_t)k * a.N + (i - n_ls);
+      dst = d.te_less_flat + (size_t)k * a.N + (i - n_ls);
+    } else {
+      src = d.cloud + (size_t)k * a.N + (i - n_ls - n_lf);
+      dst = d.te_cloud + (size_t)k * a.N + (i - n_ls - n_lf);
+    }
+    const P4 p = ld4(src);
+    const P4 us = transform_to_start_s(p, x, (double)rel_ds(p.i) / kScanPeriod);
+    const D3 e = qrot(qi, D3{(double)us.x - x[4], (double)us.y - x[5], (double)us.z - x[6]});
+    st4(dst, P4{(float)e.x, (float)e.y, (float)e.z, (float)int(p.i)});
+  }
+}
+
+// The index of the to-end clouds of exactly the scans a round solved: two workgroups per chain run
+// k_target_index_all's bodies (less-flat: 32 keys per lane; less-sharp: 16) on that chain's scan.
+// `at`: the call's OdomArgs with less_sharp / less_flat / idx_ls / idx_lf pointing at the to-end
+// clouds and their index.  r < 0: scan id_scan (one chain).
+__global__ __launch_bounds__(512, LISLAM_TI_WPE32) void k_target_index_round(OdomArgs at, int r, int id_scan) {
+  __shared__ uint64_t xch[8 * 8 * 64];
+  __shared__ float red[6][8];
+  int k = id_scan;
+  if (r >= 0 && !pair_of(at, at.c0 + (int)(blockIdx.x >> 1), r, &k)) return;
+  if (blockIdx.x & 1)
+    target_index_body<8, 16>(at, 3 * k, 3, 0, 2, 3, xch, red);  // workgroup 0 of scan k's three: the less-sharp cloud
+  else
+    target_index_body<8, 32>(at, k, 1, 1, 1, 1, xch, red);
 }
 
 __global__ void k_odom_init(OdomArgs a) {
@@ -3707,10 +3843,30 @@ void launch_target_index(const OdomArgs& a, int n_scans, hipStream_t st) {
   hipLaunchKernelGGL((k_target_index<8, 16>), dim3(3 * n_scans), dim3(512), 0, st, a, 3, 0, 2, 3);
 }
 
+// `a` with the to-end clouds and their index as the targets (mode 2).
+static OdomArgs to_end_targets(const OdomArgs& a, const DeskewPlan& p) {
+  OdomArgs at = a;
+  at.less_sharp = p.d.te_less_sharp;
+  at.less_flat = p.d.te_less_flat;
+  at.idx_ls = p.te_ls;
+  at.idx_lf = p.te_lf;
+  return at;
+}
+
+static int to_end_blocks(const OdomArgs& a) {  // 256 threads x 4 points over the three clouds' capacity
+  return max(1, min(64, (a.cap_less_sharp + 2 * a.N + 1023) / 1024));
+}
+
+void launch_to_end_identity(const OdomArgs& a, const DeskewPlan& p, int scan, hipStream_t st) {
+  hipLaunchKernelGGL(k_odom_to_end, dim3(to_end_blocks(a), 1), dim3(256), 0, st, a, p.d, -1, scan);
+  hipLaunchKernelGGL(k_target_index_round, dim3(2), dim3(512), 0, st, to_end_targets(a, p), -1, scan);
+}
+
 void launch_odometry(const OdomArgs& a0, const hipStream_t* streams, int ngroups, hipEvent_t fork,
                      const hipEvent_t* join, std::vector<OdoTimed>* ev, hipEvent_t (*get_event)(void*),
-                     void* owner) {
+                     void* owner, const DeskewPlan* deskew) {
   if (a0.n_chains <= 0) return;
+  const int mode = deskew ? deskew->mode : 0;
   const hipStream_t st = streams[0];
   hipLaunchKernelGGL(k_odom_init, dim3((a0.n_chains + 63) / 64), dim3(64), 0, st, a0);
   const int G = max(1, min(ngroups, a0.n_chains));
@@ -3735,11 +3891,33 @@ void launch_odometry(const OdomArgs& a0, const hipStream_t* streams, int ngroups
         a.cn = (int)((long)a0.n_chains * (g + 1) / G) - a.c0;
         const hipStream_t s = streams[g];
         const int cb = a.cn >= 8 ? (a.cn + 7) / 8 * 8 : a.cn;
+        if (mode != 0) {
+          // mode 2: pair k searches scan k - 1's to-end clouds; a batch chain's first scan is searched as
+          // extraction left it (the identity para: the same xyz, and the searches read int(intensity))
+          const bool te = mode == 2 && (r > 0 || deskew->round0_to_end);
+          const OdomArgs as = te ? to_end_targets(a, *deskew) : a;
+          timed(4, s, [&] {
+            hipLaunchKernelGGL((k_odom_assoc16<2, 1>), dim3(qblocks16 * cb), dim3(128), 0, s, as, r, qblocks16,
+                               DeskewArgsT<1>{deskew->d});
+          });
+          timed(5, s, [&] {
+            hipLaunchKernelGGL(k_odom_lm2<1>, dim3(a.cn), dim3(kLm2Threads), 0, s, a, r, outer, DeskewArgsT<1>{deskew->d});
+          });
+          if (mode == 2 && outer == 1) {
+            timed(7, s, [&] {
+              hipLaunchKernelGGL(k_odom_to_end, dim3(to_end_blocks(a), a.cn), dim3(256), 0, s, a, deskew->d, r, 0);
+            });
+            timed(8, s, [&] {
+              hipLaunchKernelGGL(k_target_index_round, dim3(2 * a.cn), dim3(512), 0, s, to_end_targets(a, *deskew), r, 0);
+            });
+          }
+          continue;
+        }
         timed(4, s, [&] {
-          hipLaunchKernelGGL(k_odom_assoc16<2>, dim3(qblocks16 * cb), dim3(128), 0, s, a, r, qblocks16);
+          hipLaunchKernelGGL((k_odom_assoc16<2, 0>), dim3(qblocks16 * cb), dim3(128), 0, s, a, r, qblocks16, DeskewArgsT<0>{});
         });
         timed(5, s, [&] {
-          hipLaunchKernelGGL(k_odom_lm2, dim3(a.cn), dim3(kLm2Threads), 0, s, a, r, outer);
+          hipLaunchKernelGGL(k_odom_lm2<0>, dim3(a.cn), dim3(kLm2Threads), 0, s, a, r, outer, DeskewArgsT<0>{});
         });
       }
     }

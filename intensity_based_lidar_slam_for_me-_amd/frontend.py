@@ -69,6 +69,17 @@ class Context:
         holds a lone request for a partner (deterministic pairs: tests).  Results are the same."""
         nat.check(self.lib.lislam_set_engine_pairing(self.h, int(mode)), self.h, "lislam_set_engine_pairing")
 
+    DISTORTION_OFF, DISTORTION_QUERIES, DISTORTION_TO_END = 0, 1, 2  # lislam_set_distortion
+
+    def set_distortion(self, mode: int):
+        """lislam_set_distortion: the reference's `#define DISTORTION` (laserOdometry.cpp:82) for
+        Batch.odometry and LaserOdometry.step.  DISTORTION_OFF (default): s = 1.  DISTORTION_QUERIES:
+        DISTORTION 1 as the file compiles (s per query point in TransformToStart and the cost functors).
+        DISTORTION_TO_END: that plus the block :762-790 enabled (TransformToEnd; pair k searches scan
+        k - 1's de-skewed clouds, native.OUT_CORNER_LAST / OUT_SURF_LAST / OUT_FULL_RES_END).  Modes
+        other than OFF run on the per-round launches whatever set_odometry_schedule says."""
+        nat.check(self.lib.lislam_set_distortion(self.h, int(mode)), self.h, "lislam_set_distortion")
+
     def masked_queues(self) -> int:
         """CU-masked streams (hardware queues) the library holds on this context's device
         (lislam_device_queue_count)."""
@@ -329,7 +340,9 @@ class Batch:
            nat.OUT_POSE: (np.float64, 1), nat.OUT_STATS: (np.int32, 1), nat.OUT_ORB_T: (np.float64, 1),
            nat.OUT_ORB_STATS: (np.int32, 1), nat.OUT_ORB_KEYPOINTS: (np.float32, 6), nat.OUT_ORB_POINTS: (np.float32, 4),
            nat.OUT_ORB_DESCRIPTORS: (np.uint8, 32), nat.OUT_GROUND: (np.float32, 4),
-           nat.OUT_GROUND_PLANE: (np.float32, 1), nat.OUT_GROUND_INFO: (np.int32, 1)}
+           nat.OUT_GROUND_PLANE: (np.float32, 1), nat.OUT_GROUND_INFO: (np.int32, 1),
+           nat.OUT_CORNER_LAST: (np.float32, 4), nat.OUT_SURF_LAST: (np.float32, 4),
+           nat.OUT_FULL_RES_END: (np.float32, 4)}
 
     def download(self, what: int, scan: int) -> np.ndarray:
         dt, w = self._DT[what]

@@ -22,9 +22,11 @@ OUT_SHARP, OUT_LESS_SHARP, OUT_FLAT, OUT_LESS_FLAT = 7, 8, 9, 10
 OUT_PARA, OUT_POSE, OUT_STATS = 11, 12, 13
 OUT_ORB_T, OUT_ORB_STATS, OUT_ORB_KEYPOINTS, OUT_ORB_POINTS, OUT_ORB_DESCRIPTORS = 14, 15, 16, 17, 18
 OUT_GROUND, OUT_GROUND_PLANE, OUT_GROUND_INFO = 19, 20, 21
+OUT_CORNER_LAST, OUT_SURF_LAST, OUT_FULL_RES_END = 22, 23, 24  # after odometry in DISTORTION_TO_END only
+DISTORTION_OFF, DISTORTION_QUERIES, DISTORTION_TO_END = 0, 1, 2  # lislam_set_distortion
 
 KERNELS = ("k_scan_front", "k_scan_lines", "k_scan_compact", "k_target_index", "k_odom_assoc", "k_odom_lm",
-           "k_odom_chain")
+           "k_odom_chain", "k_odom_to_end", "k_target_index_round")
 
 EXPORTED_SYMBOLS = (
     "lislam_ctx_create", "lislam_ctx_destroy", "lislam_last_error", "lislam_synchronize",
@@ -34,7 +36,7 @@ EXPORTED_SYMBOLS = (
     "lislam_batch_odometry", "lislam_batch_set_timing", "lislam_batch_kernel_times",
     "lislam_batch_download", "lislam_eval_factors", "lislam_eval_factors_raw", "lislam_set_tie_order", "lislam_set_odometry_schedule", "lislam_set_engine_shape", "lislam_batch_odometry_status",
     "lislam_batch_odometry_engine", "lislam_batch_odometry_abort_code", "lislam_device_queue_count",
-    "lislam_set_engine_pairing", "lislam_batch_odometry_paired",
+    "lislam_set_engine_pairing", "lislam_batch_odometry_paired", "lislam_set_distortion",
     "lislam_map_create", "lislam_map_destroy", "lislam_map_build", "lislam_map_add_points", "lislam_map_size",
     "lislam_map_points", "lislam_map_nearest_search", "lislam_map_associate", "lislam_normal_equations",
     "lislam_pose_solve", "lislam_voxel_grid", "lislam_mapopt_step", "lislam_mapopt_step_corner", "lislam_laser_mapping",
@@ -191,6 +193,7 @@ def load(path: str = LIB_PATH):
     L.lislam_batch_odometry_status.argtypes = [vp, ctypes.POINTER(_i32)]
     L.lislam_batch_odometry_engine.argtypes = [vp, ctypes.POINTER(_i32)]
     L.lislam_set_engine_pairing.argtypes = [vp, _i32]
+    L.lislam_set_distortion.argtypes = [vp, _i32]
     L.lislam_batch_odometry_paired.argtypes = [vp, ctypes.POINTER(_i32)]
     L.lislam_batch_odometry_abort_code.argtypes = [vp, ctypes.POINTER(_i32)]
     L.lislam_device_queue_count.argtypes = [_i32, ctypes.POINTER(_i32)]
