@@ -41,6 +41,7 @@
  *   lislam_loop_icp           <- loopClosureThread's USE_ICP block     src/intensity_feature_tracker.cpp:217-366
  *   lislam_odom_fuse          <- odomHandler callback                 src/odom_handler_node.cpp:44-132
  *   lislam_place_*            <- SCManager (Scan Context)             src/Scancontext.cpp:126-344
+ *   lislam_bow_*              <- detectLoop's DBoW3 query (ORB words)  src/loop_closure_handler.cpp:127-188
  *   lislam_pgo_*              <- the gtsam factor graph + updatePoses  src/intensity_feature_tracker.cpp:110-145,
  *                                                                      :314-381, :395-583
  */
@@ -571,6 +572,62 @@ int lislam_place_distance(lislam_place* p, const int32_t* a, const int32_t* b, i
 #define LISLAM_PLACE_SECTOR_KEY 2 /* double [S] */
 /* One output of entry index into dst (cap elements); *n = the element count. */
 int lislam_place_download(lislam_place* p, int32_t what, int32_t index, void* dst, int32_t cap, int32_t* n);
+
+/* ---- ORB bag-of-words loop detection: loopClosureHandler::detectLoop (src/loop_closure_handler.cpp:127-188,
+ * USE_ORBLOOP, called at :108-111) with its DBoW3 database device-resident.  DBoW3 is restated from the
+ * published library for the combination the reference runs: TF_IDF weights, L1_NORM scoring, no direct
+ * index (db_.setVocabulary(*voc_, false, 0)).  Entry k is the k-th image added (DBoW3's EntryId).
+ *
+ * The vocabulary is handed in as three host arrays over its n_nodes tree nodes, node 0 the root.  From a
+ * loaded DBoW3::Vocabulary (config/orbvoc.dbow3; reading its file formats is the caller's host-side work):
+ * parent[i] = m_nodes[i].parent (-1 for the root), descriptor[i] = the 32 bytes of m_nodes[i].descriptor
+ * (CV_8U 1 x 32; unused for the root), weight[i] = m_nodes[i].weight (read for leaves only).  A node's
+ * children are visited in ascending node id; a leaf's word id is its rank among leaves in ascending node
+ * id (createWords).  Required: parent[0] == -1, 0 <= parent[i] < i, 1..64 children per inner node, finite
+ * weights >= 0; otherwise LISLAM_ERR_ARG with a lislam_last_error text. */
+typedef struct lislam_bow lislam_bow;
+typedef struct {
+  double min_loop_bow_threshold; /* th: detectLoop's MIN_LOOP_BOW_TH (0.0155) */
+  double index_score_threshold;  /* the score a lower id must exceed to take over (0.015) */
+  int32_t min_loop_search_gap;   /* gap: MIN_LOOP_SEARCH_GAP (50) */
+  int32_t max_results;           /* results per query (4), 1..16 */
+  int32_t min_frame_index;       /* a loop is reported only when i > this (5) */
+  int32_t loop_index_bound;      /* ... and only to an entry id below this (6) */
+} lislam_bow_config;
+/* cfg == NULL: the values in brackets, the ones detectLoop compiles with (config/spot.yaml's 0.013 and 20
+ * are a caller's choice).  capacity = the most entries; max_features = the most descriptors of one image
+ * (1..2048). */
+int lislam_bow_create(lislam_ctx* ctx, int32_t n_nodes, const int32_t* parent, const uint8_t* descriptor, const double* weight,
+                      const lislam_bow_config* cfg, int32_t capacity, int32_t max_features, lislam_bow** out);
+int lislam_bow_destroy(lislam_bow* p);
+int lislam_bow_size(lislam_bow* p, int32_t* n);
+/* Database::add of n_images images: desc = their packed 32-byte descriptor rows one image after the other
+ * (host or device memory), counts[n_images] (host) their row counts.  An image without descriptors, or
+ * whose words all weigh 0, still takes an id (an empty vector).  counts[k] > max_features is
+ * LISLAM_ERR_ARG, more entries than the capacity LISLAM_ERR_CAPACITY; neither adds anything. */
+int lislam_bow_add(lislam_bow* p, const void* desc, const int32_t* counts, int32_t n_images);
+/* The same for the descriptors LISLAM_OUT_ORB_DESCRIPTORS reports of scans [first_scan, first_scan +
+ * n_scans) of a batch of the same context, read (count included) where they lie on the device.
+ * LISLAM_ERR_STATE unless lislam_batch_intensity_odometry has run over those scans; LISLAM_ERR_ARG for a
+ * batch of another context or one that detects more than max_features features.  Asynchronous. */
+int lislam_bow_add_batch(lislam_bow* p, lislam_batch* b, int32_t first_scan, int32_t n_scans);
+/* detectLoop as it returned when entry k was the newest and had been called once per entry before, for k
+ * in [first, first + n): loop_id[n] (-1: none) and the query behind it, db_.query(desc, ret, max_results,
+ * k - gap): n_ret[n] results, ret_id / ret_score [n][max_results] best first (unused slots -1 / 0).
+ * Equal scores come lower id first (DBoW3 leaves them to std::sort).  At k - gap == -1 the query is
+ * unrestricted (Database::query's max_id == -1) and its results are reported although loop_id is -1.
+ * Host arrays, each nullable.  The result for k depends on entries < k only. */
+int lislam_bow_detect(lislam_bow* p, int32_t first, int32_t n, int32_t* loop_id, int32_t* n_ret, int32_t* ret_id,
+                      double* ret_score);
+/* L1Scoring::score of the vectors of entries a[k] and b[k] (host arrays), in [0, 1]. */
+int lislam_bow_score(lislam_bow* p, const int32_t* a, const int32_t* b, int32_t n_pairs, double* score);
+/* Vocabulary::transform(feature, id, weight) of n descriptors (host or device memory): word_id[n],
+ * weight[n] (host, nullable). */
+int lislam_bow_transform(lislam_bow* p, const void* desc, int32_t n, int32_t* word_id, double* weight);
+#define LISLAM_BOW_WORDS 0  /* int32  [len] ascending word ids of one entry's BoW vector */
+#define LISLAM_BOW_VALUES 1 /* double [len] their L1-normalized values */
+/* One output of entry index into dst (cap elements); *n = the element count. */
+int lislam_bow_download(lislam_bow* p, int32_t what, int32_t index, void* dst, int32_t cap, int32_t* n);
 
 /* ---- Pose-graph optimization: the factor graph of feature_tracker::mapOdomHandle / loopClosureThread
  * (src/intensity_feature_tracker.cpp:395-583, :314-381) as a device-resident least-squares problem,

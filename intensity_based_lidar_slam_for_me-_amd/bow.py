@@ -1,0 +1,127 @@
+"""ORB bag-of-words loop detection over the lislam C ABI: ``loopClosureHandler::detectLoop``
+(``src/loop_closure_handler.cpp:127-188``, the ``USE_ORBLOOP`` detector that ``keyframeProcessor``
+runs at ``:108-111``) with its DBoW3 database device-resident.
+
+``BowDatabase.add_batch`` turns the ORB descriptors of a batch's scans into BoW vectors where they
+lie on the device; ``detect`` replays ``detectLoop`` for a whole range of keyframes in one call.
+``loop_id`` is what ``loop.loop_closure_icp`` takes as its history keyframe.  The vocabulary is
+handed in as arrays (``parent``, ``descriptor``, ``weight`` per tree node); reading DBoW3's files is
+the caller's work.  All compute runs in ``liblislam.so`` on the GPU; there is no CPU fallback.
+"""
+from __future__ import annotations
+
+import ctypes
+from typing import NamedTuple
+
+import numpy as np
+
+from . import native as nat
+
+BowConfig = nat.BowConfig
+
+
+class Detection(NamedTuple):
+    loop_id: np.ndarray  # (n,) int32, -1 = no loop
+    ids: list            # n arrays (n_ret,) int32: the query's results, best first
+    scores: list         # n arrays (n_ret,) float64
+
+
+def _rows(desc) -> np.ndarray:
+    return np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+
+
+class BowDatabase:
+    """``DBoW3::Database`` (TF_IDF, L1_NORM, no direct index) + ``detectLoop``; ``config`` = the
+    fields of ``BowConfig`` (defaults: the constants ``detectLoop`` compiles with)."""
+
+    def __init__(self, ctx, parent, descriptor, weight, capacity: int, max_features: int = 1000, **config):
+        self.ctx = ctx
+        self.cfg = BowConfig(**config)
+        par = np.ascontiguousarray(parent, np.int32).reshape(-1)
+        des = _rows(descriptor)
+        wgt = np.ascontiguousarray(weight, np.float64).reshape(-1)
+        if des.shape[0] != par.shape[0] or wgt.shape[0] != par.shape[0]:
+            raise ValueError("parent, descriptor and weight must hold one row per node")
+        h = ctypes.c_void_p()
+        nat.check(ctx.lib.lislam_bow_create(ctx.h, par.shape[0], nat.ptr(par), nat.ptr(des), nat.ptr(wgt), ctypes.byref(self.cfg),
+                                            int(capacity), int(max_features), ctypes.byref(h)), ctx.h, "lislam_bow_create")
+        self.h = h
+        self.max_features = int(max_features)
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.lislam_bow_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __len__(self) -> int:
+        n = ctypes.c_int32()
+        nat.check(self.ctx.lib.lislam_bow_size(self.h, ctypes.byref(n)), self.ctx.h, "lislam_bow_size")
+        return n.value
+
+    def add(self, images) -> None:
+        """Database::add of each image's descriptors ((n, 32) uint8) of the list."""
+        ds = [_rows(d) for d in images]
+        if not ds:
+            return
+        counts = np.array([d.shape[0] for d in ds], np.int32)
+        rows = np.ascontiguousarray(np.concatenate(ds))
+        nat.check(self.ctx.lib.lislam_bow_add(self.h, nat.ptr(rows) if rows.size else None, nat.ptr(counts), len(ds)),
+                  self.ctx.h, "lislam_bow_add")
+
+    def add_batch(self, batch, first: int, n: int) -> None:
+        """The same for the ORB descriptors of scans [first, first + n) of a batch whose
+        intensity_odometry has run, on the device."""
+        nat.check(self.ctx.lib.lislam_bow_add_batch(self.h, batch.h, int(first), int(n)), self.ctx.h, "lislam_bow_add_batch")
+
+    def detect(self, first: int | None = None, n: int | None = None) -> Detection:
+        """detectLoop as it returned when keyframe k was the newest, k in [first, first + n)
+        (default: every keyframe), with the results of the query behind it."""
+        first = 0 if first is None else int(first)
+        n = len(self) - first if n is None else int(n)
+        m, R = max(n, 0), self.cfg.max_results
+        loop_id, n_ret = np.zeros(m, np.int32), np.zeros(m, np.int32)
+        ids, scores = np.zeros((m, R), np.int32), np.zeros((m, R), np.float64)
+        nat.check(self.ctx.lib.lislam_bow_detect(self.h, first, n, nat.ptr(loop_id), nat.ptr(n_ret), nat.ptr(ids),
+                                                 nat.ptr(scores)), self.ctx.h, "lislam_bow_detect")
+        return Detection(loop_id, [ids[k, :n_ret[k]].copy() for k in range(m)], [scores[k, :n_ret[k]].copy() for k in range(m)])
+
+    def detect_loop(self, descriptors) -> int:
+        """detectLoop for one keyframe: query, add, decide -> loop id or -1."""
+        self.add([descriptors])
+        return int(self.detect(len(self) - 1, 1).loop_id[0])
+
+    def score(self, a, b) -> np.ndarray:
+        """L1Scoring::score(vector[a[k]], vector[b[k]]) -> (n,) float64 in [0, 1]."""
+        ia = np.ascontiguousarray(np.atleast_1d(a), np.int32)
+        ib = np.ascontiguousarray(np.atleast_1d(b), np.int32)
+        if ia.shape != ib.shape:
+            raise ValueError("a and b must hold the same number of indices")
+        out = np.zeros(ia.shape[0], np.float64)
+        nat.check(self.ctx.lib.lislam_bow_score(self.h, nat.ptr(ia), nat.ptr(ib), ia.shape[0], nat.ptr(out)), self.ctx.h,
+                  "lislam_bow_score")
+        return out
+
+    def transform(self, descriptors):
+        """Vocabulary::transform of each descriptor -> (word_id (n,) int32, weight (n,) float64)."""
+        rows = _rows(descriptors)
+        word, weight = np.zeros(rows.shape[0], np.int32), np.zeros(rows.shape[0], np.float64)
+        nat.check(self.ctx.lib.lislam_bow_transform(self.h, nat.ptr(rows) if rows.size else None, rows.shape[0], nat.ptr(word),
+                                                    nat.ptr(weight)), self.ctx.h, "lislam_bow_transform")
+        return word, weight
+
+    def _download(self, what, index, dtype):
+        buf = np.zeros(self.max_features, dtype)
+        n = ctypes.c_int32()
+        nat.check(self.ctx.lib.lislam_bow_download(self.h, what, int(index), nat.ptr(buf), buf.shape[0], ctypes.byref(n)),
+                  self.ctx.h, "lislam_bow_download")
+        return buf[:n.value].copy()
+
+    def bow_vector(self, i: int):
+        """Entry i's BoW vector -> (words (len,) int32 ascending, values (len,) float64)."""
+        return self._download(nat.BOW_WORDS, i, np.int32), self._download(nat.BOW_VALUES, i, np.float64)

@@ -118,6 +118,12 @@ int lislam_ground_batch_output(lislam_batch* b, int what, int scan, const void**
 void lislam_free_orb(void* p);
 // Device source of the ORB outputs (LISLAM_OUT_ORB_*) of one scan (lislam_orb.hip).
 int lislam_orb_batch_output(lislam_batch* b, int what, int scan, const void** src, int* cnt, size_t* esz);
+// The first-detection descriptors of every scan where they lie on the device (lislam_orb.hip): scan s
+// holds counts[s] (a device array) rows of 32 bytes from desc + s * cap * 32, never more than
+// nfeatures; n_scans = the scans the last lislam_batch_intensity_odometry covered.
+// LISLAM_ERR_STATE before that call.  The context stream is ordered after their producers.
+int lislam_orb_batch_descriptors(lislam_batch* b, const uint8_t** desc, const int** counts, int* cap, int* nfeatures,
+                                 int* n_scans);
 // Resolves a pending device-decided ORB cascade (lislam_orb.hip): waits for its verdict and, if it
 // did not converge, redoes the batch from the images it was given.  lislam_batch_extract calls it
 // before it overwrites those images.

@@ -2349,6 +2349,7 @@ struct OrbBatch {
   hipEvent_t settled = nullptr;
   bool pending = false;
   int pending_n = 0;
+  int ran_n = 0;             // scans of the last lislam_batch_intensity_odometry (lislam_orb_batch_descriptors)
   int info[2] = {-1, 0};     // lislam_batch_orb_cascade_info
   ~OrbBatch() {
     if (side) (void)hipStreamSynchronize(side);
@@ -2606,6 +2607,7 @@ int lislam_batch_intensity_odometry(lislam_batch* b, int32_t n_scans, int32_t nf
     OCHK(c, hipEventRecord(ob->done, side));
     OCHK(c, hipStreamWaitEvent(main_stream, ob->done, 0));
   }
+  ob->ran_n = rc == LISLAM_OK ? n_scans : 0;
   return rc;
 }
 
@@ -2789,4 +2791,17 @@ int lislam_orb_batch_output(lislam_batch* b, int what, int scan, const void** sr
     }
   }
   return LISLAM_ERR_ARG;
+}
+
+int lislam_orb_batch_descriptors(lislam_batch* b, const uint8_t** desc, const int** counts, int* cap, int* nfeatures,
+                                 int* n_scans) {
+  OrbBatch* ob = static_cast<OrbBatch*>(b->orb);
+  if (!ob || ob->ran_n == 0) return LISLAM_ERR_STATE;
+  ORC(orb_settle(b));
+  *desc = ob->e1->desc;
+  *counts = ob->e1->nkp;
+  *cap = ob->e1->g.cap;
+  *nfeatures = ob->nfeatures;
+  *n_scans = ob->ran_n;
+  return LISLAM_OK;
 }

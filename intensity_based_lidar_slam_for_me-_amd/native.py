@@ -47,6 +47,8 @@ EXPORTED_SYMBOLS = (
     "lislam_batch_odometry_gated", "lislam_odom_step_gated", "lislam_batch_mapopt", "lislam_batch_mapopt_corner", "lislam_loop_icp", "lislam_odom_fuser_create", "lislam_odom_fuser_destroy", "lislam_odom_fuse",
     "lislam_place_create", "lislam_place_destroy", "lislam_place_size", "lislam_place_add_clouds", "lislam_place_add_batch",
     "lislam_place_detect", "lislam_place_distance", "lislam_place_download",
+    "lislam_bow_create", "lislam_bow_destroy", "lislam_bow_size", "lislam_bow_add", "lislam_bow_add_batch",
+    "lislam_bow_detect", "lislam_bow_score", "lislam_bow_transform", "lislam_bow_download",
     "lislam_pgo_create", "lislam_pgo_destroy", "lislam_pgo_size", "lislam_pgo_add_nodes", "lislam_pgo_set_prior",
     "lislam_pgo_add_edges", "lislam_pgo_add_batch", "lislam_pgo_edges", "lislam_pgo_linearize", "lislam_pgo_optimize",
     "lislam_pgo_poses",
@@ -60,6 +62,8 @@ MAP_KERNELS = ("k_knn", "k_fit", "k_lm_eval", "k_lm_step", "map_rebuild", "map_d
 MATCH_LINE, MATCH_PLANE = 0, 1
 PLACE_DESC, PLACE_RING_KEY, PLACE_SECTOR_KEY = 0, 1, 2
 PLACE_KERNELS = ("k_sc_describe", "k_sc_finish", "k_sc_detect", "k_sc_distance")
+BOW_WORDS, BOW_VALUES = 0, 1
+BOW_KERNELS = ("k_bow_words", "k_bow_vector", "k_bow_query", "k_bow_select", "k_bow_score", "k_bow_gather")
 PGO_CONVERGED, PGO_LAMBDA_LIMIT, PGO_MAX_ITERATIONS = 0, 1, 2
 PGO_KERNELS = ("k_pgo_linearize", "k_pgo_assemble", "k_pgo_sum", "k_pgo_factor", "k_pgo_cg", "k_pgo_retract",
                "k_pgo_add_batch", "k_pgo_pose6d")
@@ -121,6 +125,19 @@ class PlaceConfig(ctypes.Structure):
                  num_exclude_recent=50, num_candidates=10, tree_making_period=50):
         super().__init__(lidar_height, max_radius, search_ratio, dist_thres, num_ring, num_sector, num_exclude_recent,
                          num_candidates, tree_making_period)
+
+
+class BowConfig(ctypes.Structure):
+    """lislam_bow_config: detectLoop's thresholds; defaults = the constants it compiles with
+    (loop_closure_handler.cpp:127-188)."""
+
+    _fields_ = [("min_loop_bow_threshold", ctypes.c_double), ("index_score_threshold", ctypes.c_double),
+                ("min_loop_search_gap", _i32), ("max_results", _i32), ("min_frame_index", _i32), ("loop_index_bound", _i32)]
+
+    def __init__(self, min_loop_bow_threshold=0.0155, index_score_threshold=0.015, min_loop_search_gap=50, max_results=4,
+                 min_frame_index=5, loop_index_bound=6):
+        super().__init__(min_loop_bow_threshold, index_score_threshold, min_loop_search_gap, max_results, min_frame_index,
+                         loop_index_bound)
 
 
 class PgoConfig(ctypes.Structure):
@@ -242,6 +259,15 @@ def load(path: str = LIB_PATH):
     L.lislam_place_detect.argtypes = [vp, _i32, _i32, vp, vp, vp, vp, vp]
     L.lislam_place_distance.argtypes = [vp, vp, vp, _i32, vp, vp]
     L.lislam_place_download.argtypes = [vp, _i32, _i32, vp, _i32, _i32p]
+    L.lislam_bow_create.argtypes = [vp, _i32, vp, vp, vp, ctypes.POINTER(BowConfig), _i32, _i32, ctypes.POINTER(vp)]
+    L.lislam_bow_destroy.argtypes = [vp]
+    L.lislam_bow_size.argtypes = [vp, _i32p]
+    L.lislam_bow_add.argtypes = [vp, vp, vp, _i32]
+    L.lislam_bow_add_batch.argtypes = [vp, vp, _i32, _i32]
+    L.lislam_bow_detect.argtypes = [vp, _i32, _i32, vp, vp, vp, vp]
+    L.lislam_bow_score.argtypes = [vp, vp, vp, _i32, vp]
+    L.lislam_bow_transform.argtypes = [vp, vp, _i32, vp, vp]
+    L.lislam_bow_download.argtypes = [vp, _i32, _i32, vp, _i32, _i32p]
     L.lislam_pgo_create.argtypes = [vp, ctypes.POINTER(PgoConfig), _i32, _i32, ctypes.POINTER(vp)]
     L.lislam_pgo_destroy.argtypes = [vp]
     L.lislam_pgo_size.argtypes = [vp, _i32p, _i32p]
