@@ -42,6 +42,7 @@
  *   lislam_odom_fuse          <- odomHandler callback                 src/odom_handler_node.cpp:44-132
  *   lislam_place_*            <- SCManager (Scan Context)             src/Scancontext.cpp:126-344
  *   lislam_bow_*              <- detectLoop's DBoW3 query (ORB words)  src/loop_closure_handler.cpp:127-188
+ *   lislam_bow_train(er_*)    <- DBoW3::Vocabulary::create: the tree    src/loop_closure_handler.cpp:12-17 loads from a file
  *   lislam_pgo_*              <- the gtsam factor graph + updatePoses  src/intensity_feature_tracker.cpp:110-145,
  *                                                                      :314-381, :395-583
  */
@@ -628,6 +629,81 @@ int lislam_bow_transform(lislam_bow* p, const void* desc, int32_t n, int32_t* wo
 #define LISLAM_BOW_VALUES 1 /* double [len] their L1-normalized values */
 /* One output of entry index into dst (cap elements); *n = the element count. */
 int lislam_bow_download(lislam_bow* p, int32_t what, int32_t index, void* dst, int32_t cap, int32_t* n);
+
+/* ---- Vocabulary training: DBoW3::Vocabulary::create (hierarchical k-means++ over the binary descriptors,
+ * then TF_IDF word weights), restated from the published library (Vocabulary.cpp: HKmeansStep,
+ * initiateClustersKMpp, createWords, setNodeWeights; DescManip::meanValue).  A trainer collects the
+ * descriptors of many images on the device; lislam_bow_train turns them into the (parent, descriptor,
+ * weight) arrays lislam_bow_create takes, node ids in DBoW3's order (a step appends all its children,
+ * then recurses into child 0, child 1, ...: parent[i] < i, the children of a node consecutive).
+ *
+ * One step, on a node's descriptors in their original order (image, then row): with at most k of them
+ * each becomes its own child; otherwise k-means++ seeds up to k centres (plain Hamming distances, all
+ * integers; it stops early when every descriptor equals a centre), every descriptor goes to the first
+ * centre at the smallest distance, and (bit-majority means, assignment) repeat until an assignment
+ * equals the one before.  A child is clustered in turn if it holds more than one descriptor and its
+ * level is below L.  weight = log(N / Ni), N = the images added (empty ones too), Ni = the images in
+ * which the word occurs; 0 for Ni == 0 and for inner nodes.
+ *
+ * Three points are this library's own, because DBoW3 leaves them open or cannot be replayed in parallel:
+ *  - random draws do not follow rand() in visiting order but a counter-based generator keyed by the node:
+ *      splitmix64(x): z = x + 0x9E3779B97F4A7C15; z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;
+ *                     z = (z ^ (z >> 27)) * 0x94D049BB133111EB; return z ^ (z >> 31)
+ *      key(root) = splitmix64(seed), key(child slot c) = splitmix64(key(parent) ^ (c + 1)),
+ *      draw j of a node = splitmix64(key + j * 0x9E3779B97F4A7C15), reduced to [0, n) as
+ *      ((x >> 32) * n) >> 32.  Draw 0 picks the first centre, draw j >= 1 the value r in [1, S] that
+ *      picks centre j (the first descriptor whose inclusive prefix sum of min-distances reaches r);
+ *  - an empty cluster keeps its centre (DBoW3's meanValue is undefined there);
+ *  - a node stops after max_iterations assignments (the seeding's is the first); DBoW3 has no limit. */
+typedef struct lislam_bow_trainer lislam_bow_trainer;
+typedef struct {
+  int32_t k;              /* children per node, 2..64 */
+  int32_t L;              /* levels below the root, 1..10 */
+  int32_t max_iterations; /* >= 1 */
+  uint64_t seed;
+} lislam_bow_train_config;
+#define LISLAM_BOW_TRAIN_MAX_L 10
+#define LISLAM_BOW_TRAIN_MAX_DESCRIPTORS (1 << 23) /* every sum of distances fits 31 bits */
+#define LISLAM_BOW_PHASE_SEED 0
+#define LISLAM_BOW_PHASE_ASSIGN 1
+#define LISLAM_BOW_PHASE_MEANS 2
+#define LISLAM_BOW_PHASE_PARTITION 3
+typedef struct {
+  int32_t profile; /* in: nonzero = wait for the device after every phase and fill phase_ms (slower) */
+  int32_t n_nodes, n_words, n_zero_words; /* the root included; leaves; leaves of weight 0 */
+  int32_t n_levels;                       /* levels that held a node to cluster, <= L */
+  /* per level (index 0 = the root's step): steps run, those with more than k descriptors (k-means), the
+   * largest iteration count among them (0 if none), how many of them stopped at max_iterations */
+  int32_t level_steps[LISLAM_BOW_TRAIN_MAX_L], level_clustered[LISLAM_BOW_TRAIN_MAX_L];
+  int32_t level_iterations[LISLAM_BOW_TRAIN_MAX_L], level_capped[LISLAM_BOW_TRAIN_MAX_L];
+  double level_ms[LISLAM_BOW_TRAIN_MAX_L];    /* host wall clock of the level */
+  double phase_ms[LISLAM_BOW_TRAIN_MAX_L][4]; /* LISLAM_BOW_PHASE_*, only with profile */
+  double weights_ms;                          /* descent, image counts, log */
+  double total_ms;                            /* the whole call, renumbering included */
+} lislam_bow_train_stats;
+/* Room for cap_images images and cap_descriptors descriptors (<= LISLAM_BOW_TRAIN_MAX_DESCRIPTORS, else
+ * LISLAM_ERR_CAPACITY). */
+int lislam_bow_trainer_create(lislam_ctx* ctx, int32_t cap_images, int32_t cap_descriptors, lislam_bow_trainer** out);
+int lislam_bow_trainer_destroy(lislam_bow_trainer* t);
+int lislam_bow_trainer_size(lislam_bow_trainer* t, int32_t* n_images, int32_t* n_descriptors);
+/* n_images images: packed 32-byte rows one image after the other (host or device memory), counts[n_images]
+ * (host).  An image without descriptors counts towards N.  A negative count is LISLAM_ERR_ARG, more images
+ * or descriptors than there is room for LISLAM_ERR_CAPACITY; neither adds anything.  Allowed after a
+ * lislam_bow_train: the next training sees every image added so far. */
+int lislam_bow_trainer_add(lislam_bow_trainer* t, const void* desc, const int32_t* counts, int32_t n_images);
+/* The same for the descriptors LISLAM_OUT_ORB_DESCRIPTORS reports of scans [first_scan, first_scan + n_scans)
+ * of a batch of the same context, read where they lie on the device.  Errors as lislam_bow_add_batch. */
+int lislam_bow_trainer_add_batch(lislam_bow_trainer* t, lislam_batch* b, int32_t first_scan, int32_t n_scans);
+/* Vocabulary::create(k, L, TF_IDF) over everything added.  cfg == NULL: k 10, L 5 (DBoW3's constructor
+ * defaults), max_iterations 100, seed 0.  *n_nodes (nullable) = the size of the arrays; stats nullable.
+ * A trainer without descriptors trains to the root alone (n_nodes 1), a tree lislam_bow_create rejects.
+ * May be repeated with another configuration.  k, L or max_iterations out of range: LISLAM_ERR_ARG. */
+int lislam_bow_train(lislam_bow_trainer* t, const lislam_bow_train_config* cfg, int32_t* n_nodes,
+                     lislam_bow_train_stats* stats);
+/* The arrays of the last training (host, cap_nodes rows each, each nullable): what lislam_bow_create takes.
+ * LISLAM_ERR_STATE before a training, LISLAM_ERR_CAPACITY if cap_nodes is below n_nodes. */
+int lislam_bow_trainer_vocabulary(lislam_bow_trainer* t, int32_t cap_nodes, int32_t* parent, uint8_t* descriptor,
+                                  double* weight);
 
 /* ---- Pose-graph optimization: the factor graph of feature_tracker::mapOdomHandle / loopClosureThread
  * (src/intensity_feature_tracker.cpp:395-583, :314-381) as a device-resident least-squares problem,

@@ -5,10 +5,10 @@ name is not a Python identifier).  The compute path is the HIP library ``liblisl
 ``__graft_entry__.build()``; there is no CPU fallback.
 """
 from . import bow, intensity, loop, mapping, native, place, posegraph, synth  # noqa: F401
-from .bow import BowDatabase  # noqa: F401
+from .bow import BowDatabase, BowTrainer, Vocabulary  # noqa: F401
 from .place import ScanContext  # noqa: F401
 from .posegraph import PoseGraph  # noqa: F401
 from .frontend import Batch, Context, Features, ImageHandler, LaserOdometry, ScanRegistration, eval_factors  # noqa: F401
 
-__all__ = ["bow", "intensity", "loop", "mapping", "native", "place", "posegraph", "synth", "Batch", "BowDatabase", "Context", "Features", "ImageHandler", "LaserOdometry",
-           "PoseGraph", "ScanContext", "ScanRegistration", "eval_factors"]
+__all__ = ["bow", "intensity", "loop", "mapping", "native", "place", "posegraph", "synth", "Batch", "BowDatabase", "BowTrainer", "Context", "Features", "ImageHandler", "LaserOdometry",
+           "PoseGraph", "ScanContext", "ScanRegistration", "Vocabulary", "eval_factors"]

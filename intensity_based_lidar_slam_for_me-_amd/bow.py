@@ -6,7 +6,9 @@ runs at ``:108-111``) with its DBoW3 database device-resident.
 lie on the device; ``detect`` replays ``detectLoop`` for a whole range of keyframes in one call.
 ``loop_id`` is what ``loop.loop_closure_icp`` takes as its history keyframe.  The vocabulary is
 handed in as arrays (``parent``, ``descriptor``, ``weight`` per tree node); reading DBoW3's files is
-the caller's work.  All compute runs in ``liblislam.so`` on the GPU; there is no CPU fallback.
+the caller's work, or trained here: ``BowTrainer`` is ``DBoW3::Vocabulary::create`` (hierarchical
+k-means++ and TF-IDF weights) over the descriptors this front end produces, on the device.  All
+compute runs in ``liblislam.so`` on the GPU; there is no CPU fallback.
 """
 from __future__ import annotations
 
@@ -18,6 +20,7 @@ import numpy as np
 from . import native as nat
 
 BowConfig = nat.BowConfig
+BowTrainConfig = nat.BowTrainConfig
 
 
 class Detection(NamedTuple):
@@ -125,3 +128,97 @@ class BowDatabase:
     def bow_vector(self, i: int):
         """Entry i's BoW vector -> (words (len,) int32 ascending, values (len,) float64)."""
         return self._download(nat.BOW_WORDS, i, np.int32), self._download(nat.BOW_VALUES, i, np.float64)
+
+
+class Vocabulary(NamedTuple):
+    parent: np.ndarray      # (n_nodes,) int32, -1 for the root; parent[i] < i, children consecutive
+    descriptor: np.ndarray  # (n_nodes, 32) uint8
+    weight: np.ndarray      # (n_nodes,) float64: log(N / Ni) for words, 0 for inner nodes
+
+
+class TrainStats(NamedTuple):
+    n_nodes: int
+    n_words: int
+    n_zero_words: int
+    level_steps: list       # per level that ran: HKmeansStep calls
+    level_clustered: list   # ... of which with more than k descriptors (k-means)
+    level_iterations: list  # ... their largest iteration count
+    level_capped: list      # ... how many stopped at max_iterations
+    level_ms: list
+    phase_ms: list          # per level {seed, assign, means, partition}; zeros unless train(profile=True)
+    weights_ms: float
+    total_ms: float         # the whole lislam_bow_train call on the host's clock
+
+
+class BowTrainer:
+    """``DBoW3::Vocabulary::create`` (k-means++ per node, TF_IDF) over the descriptors of up to
+    ``cap_images`` images, device-resident.  The deviations from DBoW3 (keyed random draws, empty
+    clusters, the iteration cap) are in ``include/lislam.h``."""
+
+    def __init__(self, ctx, cap_images: int, cap_descriptors: int):
+        self.ctx = ctx
+        h = ctypes.c_void_p()
+        nat.check(ctx.lib.lislam_bow_trainer_create(ctx.h, int(cap_images), int(cap_descriptors), ctypes.byref(h)), ctx.h,
+                  "lislam_bow_trainer_create")
+        self.h = h
+        self.stats = None
+        self.vocabulary = None
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.lislam_bow_trainer_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def size(self):
+        """-> (images, descriptors) added so far."""
+        ni, nd = ctypes.c_int32(), ctypes.c_int32()
+        nat.check(self.ctx.lib.lislam_bow_trainer_size(self.h, ctypes.byref(ni), ctypes.byref(nd)), self.ctx.h,
+                  "lislam_bow_trainer_size")
+        return ni.value, nd.value
+
+    def add(self, images) -> None:
+        """Each image's descriptors ((n, 32) uint8) of the list; an empty image counts towards N."""
+        ds = [_rows(d) for d in images]
+        if not ds:
+            return
+        counts = np.array([d.shape[0] for d in ds], np.int32)
+        rows = np.ascontiguousarray(np.concatenate(ds))
+        nat.check(self.ctx.lib.lislam_bow_trainer_add(self.h, nat.ptr(rows) if rows.size else None, nat.ptr(counts), len(ds)),
+                  self.ctx.h, "lislam_bow_trainer_add")
+
+    def add_batch(self, batch, first: int, n: int) -> None:
+        """The ORB descriptors of scans [first, first + n) of a batch whose intensity_odometry has
+        run, read where they lie on the device."""
+        nat.check(self.ctx.lib.lislam_bow_trainer_add_batch(self.h, batch.h, int(first), int(n)), self.ctx.h,
+                  "lislam_bow_trainer_add_batch")
+
+    def train(self, k: int = 10, L: int = 5, max_iterations: int = 100, seed: int = 0, profile: bool = False) -> Vocabulary:
+        """-> Vocabulary(parent, descriptor, weight), node ids in DBoW3's order; ``stats`` is filled.
+        Without descriptors the tree is the root alone, which ``BowDatabase`` rejects."""
+        cfg = BowTrainConfig(int(k), int(L), int(max_iterations), int(seed))
+        st = nat.BowTrainStats()
+        st.profile = int(bool(profile))
+        n = ctypes.c_int32()
+        nat.check(self.ctx.lib.lislam_bow_train(self.h, ctypes.byref(cfg), ctypes.byref(n), ctypes.byref(st)), self.ctx.h,
+                  "lislam_bow_train")
+        parent, desc, weight = np.zeros(n.value, np.int32), np.zeros((n.value, 32), np.uint8), np.zeros(n.value, np.float64)
+        nat.check(self.ctx.lib.lislam_bow_trainer_vocabulary(self.h, n.value, nat.ptr(parent), nat.ptr(desc), nat.ptr(weight)),
+                  self.ctx.h, "lislam_bow_trainer_vocabulary")
+        m = st.n_levels
+        self.stats = TrainStats(st.n_nodes, st.n_words, st.n_zero_words, list(st.level_steps)[:m], list(st.level_clustered)[:m],
+                                list(st.level_iterations)[:m], list(st.level_capped)[:m], list(st.level_ms)[:m],
+                                [dict(zip(nat.BOW_PHASES, st.phase_ms[i])) for i in range(m)], st.weights_ms, st.total_ms)
+        self.vocabulary = Vocabulary(parent, desc, weight)
+        return self.vocabulary
+
+    def database(self, capacity: int, max_features: int = 1000, **config) -> BowDatabase:
+        """A ``BowDatabase`` over the vocabulary of the last ``train``."""
+        if self.vocabulary is None:
+            raise RuntimeError("BowTrainer.database: call train first")
+        return BowDatabase(self.ctx, *self.vocabulary, capacity=capacity, max_features=max_features, **config)

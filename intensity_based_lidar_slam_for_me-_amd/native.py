@@ -49,6 +49,8 @@ EXPORTED_SYMBOLS = (
     "lislam_place_detect", "lislam_place_distance", "lislam_place_download",
     "lislam_bow_create", "lislam_bow_destroy", "lislam_bow_size", "lislam_bow_add", "lislam_bow_add_batch",
     "lislam_bow_detect", "lislam_bow_score", "lislam_bow_transform", "lislam_bow_download",
+    "lislam_bow_trainer_create", "lislam_bow_trainer_destroy", "lislam_bow_trainer_size", "lislam_bow_trainer_add",
+    "lislam_bow_trainer_add_batch", "lislam_bow_train", "lislam_bow_trainer_vocabulary",
     "lislam_pgo_create", "lislam_pgo_destroy", "lislam_pgo_size", "lislam_pgo_add_nodes", "lislam_pgo_set_prior",
     "lislam_pgo_add_edges", "lislam_pgo_add_batch", "lislam_pgo_edges", "lislam_pgo_linearize", "lislam_pgo_optimize",
     "lislam_pgo_poses",
@@ -64,6 +66,10 @@ PLACE_DESC, PLACE_RING_KEY, PLACE_SECTOR_KEY = 0, 1, 2
 PLACE_KERNELS = ("k_sc_describe", "k_sc_finish", "k_sc_detect", "k_sc_distance")
 BOW_WORDS, BOW_VALUES = 0, 1
 BOW_KERNELS = ("k_bow_words", "k_bow_vector", "k_bow_query", "k_bow_select", "k_bow_score", "k_bow_gather")
+BOW_TRAIN_MAX_L, BOW_TRAIN_MAX_DESCRIPTORS = 10, 1 << 23
+BOW_PHASES = ("seed", "assign", "means", "partition")
+BOW_TRAIN_KERNELS = ("k_bowt_ingest", "k_bowt_locate", "k_bowt_seed", "k_bowt_assign", "k_bowt_means", "k_bowt_majority",
+                     "k_bowt_tilecount", "k_bowt_offsets", "k_bowt_scatter", "k_bowt_ni")
 PGO_CONVERGED, PGO_LAMBDA_LIMIT, PGO_MAX_ITERATIONS = 0, 1, 2
 PGO_KERNELS = ("k_pgo_linearize", "k_pgo_assemble", "k_pgo_sum", "k_pgo_factor", "k_pgo_cg", "k_pgo_retract",
                "k_pgo_add_batch", "k_pgo_pose6d")
@@ -125,6 +131,24 @@ class PlaceConfig(ctypes.Structure):
                  num_exclude_recent=50, num_candidates=10, tree_making_period=50):
         super().__init__(lidar_height, max_radius, search_ratio, dist_thres, num_ring, num_sector, num_exclude_recent,
                          num_candidates, tree_making_period)
+
+
+class BowTrainConfig(ctypes.Structure):
+    """lislam_bow_train_config; defaults = DBoW3's constructor (k 10, L 5)."""
+
+    _fields_ = [("k", _i32), ("L", _i32), ("max_iterations", _i32), ("seed", ctypes.c_uint64)]
+
+    def __init__(self, k=10, L=5, max_iterations=100, seed=0):
+        super().__init__(k, L, max_iterations, seed)
+
+
+class BowTrainStats(ctypes.Structure):
+    """lislam_bow_train_stats."""
+
+    _fields_ = [("profile", _i32), ("n_nodes", _i32), ("n_words", _i32), ("n_zero_words", _i32), ("n_levels", _i32),
+                ("level_steps", _i32 * 10), ("level_clustered", _i32 * 10), ("level_iterations", _i32 * 10),
+                ("level_capped", _i32 * 10), ("level_ms", ctypes.c_double * 10), ("phase_ms", (ctypes.c_double * 4) * 10),
+                ("weights_ms", ctypes.c_double), ("total_ms", ctypes.c_double)]
 
 
 class BowConfig(ctypes.Structure):
@@ -268,6 +292,13 @@ def load(path: str = LIB_PATH):
     L.lislam_bow_score.argtypes = [vp, vp, vp, _i32, vp]
     L.lislam_bow_transform.argtypes = [vp, vp, _i32, vp, vp]
     L.lislam_bow_download.argtypes = [vp, _i32, _i32, vp, _i32, _i32p]
+    L.lislam_bow_trainer_create.argtypes = [vp, _i32, _i32, ctypes.POINTER(vp)]
+    L.lislam_bow_trainer_destroy.argtypes = [vp]
+    L.lislam_bow_trainer_size.argtypes = [vp, _i32p, _i32p]
+    L.lislam_bow_trainer_add.argtypes = [vp, vp, vp, _i32]
+    L.lislam_bow_trainer_add_batch.argtypes = [vp, vp, _i32, _i32]
+    L.lislam_bow_train.argtypes = [vp, ctypes.POINTER(BowTrainConfig), _i32p, ctypes.POINTER(BowTrainStats)]
+    L.lislam_bow_trainer_vocabulary.argtypes = [vp, _i32, vp, vp, vp]
     L.lislam_pgo_create.argtypes = [vp, ctypes.POINTER(PgoConfig), _i32, _i32, ctypes.POINTER(vp)]
     L.lislam_pgo_destroy.argtypes = [vp]
     L.lislam_pgo_size.argtypes = [vp, _i32p, _i32p]
