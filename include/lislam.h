@@ -278,8 +278,17 @@ int lislam_set_engine_shape(lislam_ctx* ctx, int32_t queries_per_wave, int32_t d
 #define LISLAM_PAIRING_AUTO 1
 #define LISLAM_PAIRING_REQUIRE 2
 int lislam_set_engine_pairing(lislam_ctx* ctx, int32_t mode);
-/* *paired = 1 if the batch's last engine launch was shared with another batch's chain, else 0
- * (a settling call, see lislam_batch_odometry_status). */
+/* Engine segments (results are the same).  pairs > 0: at depth > 1 a one-chain odometry call of this
+ * context runs as engine launches of `pairs` scan pairs each (the last one shorter), each starting
+ * from the state the previous one left, and the dispatcher chooses the chain's partner
+ * (lislam_set_engine_pairing) anew for every launch: a chain that becomes ready while another runs
+ * joins it at its next segment, and one whose partner ends takes the next.  A launch that gives up
+ * ends the chain there and the whole chain is re-run as ever (lislam_batch_odometry_status).
+ * 0: whole chains, one launch each.  A new context starts from the build's LISLAM_ENGINE_SEGMENT (50).
+ * No effect at depth 1, on several chains per call or under lislam_set_distortion. */
+int lislam_set_engine_segment(lislam_ctx* ctx, int32_t pairs);
+/* *paired = 1 if the batch's last engine launch (any segment of its last chain) was shared with
+ * another batch's chain, else 0 (a settling call, see lislam_batch_odometry_status). */
 int lislam_batch_odometry_paired(lislam_batch* b, int32_t* paired);
 /* status = the number of engine launches of the batch that gave up since the previous status call
  * (one of the engine's bounded device waits expired, e.g. when its two launches could not run

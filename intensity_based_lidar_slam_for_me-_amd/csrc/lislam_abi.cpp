@@ -702,7 +702,11 @@ static int run_odometry(lislam_batch* b, int n_scans, int chain_len, const doubl
         r.pairing = c->eng_pairing;
         r.ctl_words = (size_t)8 + 10 * (size_t)b->max_scans;  // eng_ctl's allocation (alloc_batch)
         r.paired = r.held = false;
-        queued = lislam::submit_odometry_chain_split(&r) > 0;
+        // segments (lislam_set_engine_segment): one chain, whose state between two segments lies in
+        // row 1 of d_init (row 0 may hold the chain's own init state, which a re-run would need)
+        r.segment = o.n_chains == 1 && b->max_scans >= 2 ? c->eng_segment : 0;
+        r.a.resume = r.segment > 0 ? b->d_init + 14 : nullptr;
+        queued =lislam::submit_odometry_chain_split(&r) > 0;
       } else {
         queued = lislam::launch_odometry_chain_split(o, b->eng_ready, b->eng_fork, b->eng_join_r, b->eng_join_i, e0, e1,
                                                      b->h_abort, b->eng_done) > 0;
@@ -1267,6 +1271,12 @@ int lislam_set_engine_shape(lislam_ctx* c, int32_t queries_per_wave, int32_t dep
 int lislam_set_engine_pairing(lislam_ctx* c, int32_t mode) {
   if (!c || mode < LISLAM_PAIRING_OFF || mode > LISLAM_PAIRING_REQUIRE) return LISLAM_ERR_ARG;
   c->eng_pairing = mode;
+  return LISLAM_OK;
+}
+
+int lislam_set_engine_segment(lislam_ctx* c, int32_t pairs) {
+  if (!c || pairs < 0) return LISLAM_ERR_ARG;
+  c->eng_segment = pairs;
   return LISLAM_OK;
 }
 

@@ -28,6 +28,15 @@ struct lislam_ktimer {
   }
 };
 
+// A new context's engine segment (lislam_set_engine_segment), pairs per launch; 0 = whole chains.
+// A constant, as LISLAM_PAIR_HOLD_US is: the A/B's builds set it with -DLISLAM_ENGINE_SEGMENT=n.
+// 50: L = 50 and 100 lead the A/B against the hold (25 and 150 are lower), and the sustained rate
+// of the pipelined stream rises 28.4k -> 31.7k scans/s over whole chains (profiles/segment_ab.txt,
+// profiles/segment_bench_ab.txt).
+#ifndef LISLAM_ENGINE_SEGMENT
+#define LISLAM_ENGINE_SEGMENT 50
+#endif
+
 struct lislam_ctx {
   lislam_config cfg;
   int device = 0;
@@ -42,6 +51,7 @@ struct lislam_ctx {
   int odom_engine = LISLAM_ENGINE_AUTO;     // lislam_set_odometry_schedule
   int eng_qpw = 1, eng_depth = 1;           // lislam_set_engine_shape (the latency shape)
   int eng_pairing = LISLAM_PAIRING_AUTO;    // lislam_set_engine_pairing
+  int eng_segment = LISLAM_ENGINE_SEGMENT;  // lislam_set_engine_segment
   int distortion = LISLAM_DISTORTION_OFF;   // lislam_set_distortion
   // lislam_eval_factors(_raw): one grow-only device buffer for the blocks, the parameters and the
   // outputs, reused across calls; the mutex serializes callers (Ceres evaluates residual blocks

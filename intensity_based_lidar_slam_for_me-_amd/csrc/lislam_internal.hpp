@@ -110,6 +110,11 @@ struct OdomArgs {
   int* warm;          // [n_chains][cap_sharp + cap_flat][4]
   double* eng_part;   // [n_chains][engine_part_rows][32]: each association item's (and overflow query's)
                       // share of the first evaluation
+  // A resumable engine launch (a segment of the chains' rounds): round r of the launch is the
+  // chain's round r0 + r, and the solve role leaves the chain's para(7) + pose(7), init_state's
+  // layout, in `resume` (null: not kept) for the launch that runs the next rounds from it.
+  int r0;
+  double* resume;     // [n_chains][14]
 };
 
 // DISTORTION 1 (lislam_set_distortion, laserOdometry.cpp:82).  What the mode 1 / 2 kernels take
@@ -210,6 +215,17 @@ struct EngineRequest {
   bool paired = false;     // out: the launch was shared (valid once state is 2)
   bool held = false;       // the dispatcher: waiting for a partner since hold_t0
   std::chrono::steady_clock::time_point hold_t0;
+  // Segments (lislam_set_engine_segment): a one-chain request goes out as launches of `segment`
+  // rounds each (0: the whole chain in one), and the dispatcher chooses its partner anew for every
+  // one.  A segment starts where the previous one ended (OdomArgs::r0, resume; a.resume must be set)
+  // once that launch's end has been seen complete on the host with its abort words zero; a give-up
+  // ends the chain there (h_abort tells, as ever).  The request's own events are recorded by its
+  // last segment (t0 by its first), and `state` turns 2 with it; `paired`: any segment was shared.
+  int segment = 0;
+  int next_round = 0;      // the dispatcher: the chain's rounds launched so far
+  int seg_slot = -1;       // ... and the engine slot its segment in flight runs on
+  bool seg_shared = false; // ... with another request's segment
+  unsigned long long seq = 0;  // submission number: continuations are served oldest chain first
 };
 constexpr int kPairOff = 0, kPairAuto = 1, kPairRequire = 2;
 int submit_odometry_chain_split(EngineRequest* r);

@@ -755,7 +755,7 @@ __device__ __forceinline__ int rank_to_index(const LineSearch& s, int key) {
 __device__ __forceinline__ bool pair_of(const OdomArgs& a, int c, int r, int* k) {
   const int k0 = c * a.chain_len;
   const int k1 = min(k0 + a.chain_len, a.S - 1);
-  *k = k0 + r + 1;
+  *k = k0 + a.r0 + r + 1;  // r0: the launch's first round (a later segment of the chain), else 0
   return *k <= k1;
 }
 
@@ -2740,6 +2740,15 @@ __device__ __forceinline__ bool eng_solve_role(const OdomArgs& a, const EngCtl& 
     __syncthreads();
   }
   if (wave0 && lane < 7) { st[lane] = sh.cx[lane]; st[7 + lane] = sh.cpw[lane]; }  // the chain's final state
+  // ... and, for a launch that ends mid-chain, where the next segment's init_state reads it: words
+  // of their own, not `state`, which this role overwrites after pass 0 while a later segment's
+  // pass-0 items would still start from it (eng_x_word).  This launch's own init_state may be the
+  // same buffer: the role copied it above, and every live item of pass 0 read it before the pass's
+  // solve, so before this store.
+  if (wave0 && lane < 7 && a.resume) {
+    a.resume[(size_t)c * 14 + lane] = sh.cx[lane];
+    a.resume[(size_t)c * 14 + 7 + lane] = sh.cpw[lane];
+  }
   return true;
 }
 
@@ -3376,6 +3385,12 @@ struct EngineGate {
   std::condition_variable cv_req, cv_launched;
   hipEvent_t slot_ev[kMaxDepth] = {};
   bool slot_used[kMaxDepth] = {};
+  // segments (EngineRequest::segment): the requests whose launch in flight is not their chain's
+  // last, each on slot seg_slot; the slots' roles-end events (a segment that is not the last
+  // records none of its request's); requests submitted so far
+  std::vector<EngineRequest*> flying;
+  hipEvent_t slot_jr[kMaxDepth] = {};
+  unsigned long long submits = 0;
 };
 static EngineGate* engine_gate(int dev) {
   static EngineGate gates[64];
@@ -3434,7 +3449,8 @@ void release_engine_streams(int dev) {
   g->stop = false;
   for (int s = 0; s < EngineGate::kMaxDepth; s++) {
     if (g->slot_ev[s]) (void)hipEventDestroy(g->slot_ev[s]);
-    g->slot_ev[s] = nullptr;
+    if (g->slot_jr[s]) (void)hipEventDestroy(g->slot_jr[s]);
+    g->slot_ev[s] = g->slot_jr[s] = nullptr;
     g->slot_used[s] = false;
   }
   for (int s = 0; s < EngineGate::kMaxDepth; s++) {
@@ -3539,29 +3555,37 @@ static SplitPlan split_plan(const OdomArgs& a, int dev, const OdomArgs* b2 = nul
   return p;
 }
 
+// One request's part of a launch: what the launch waits for, records and copies for it.  A null
+// member is skipped: a segment that is not its chain's first records no t0, one that is not its
+// last none of join_r / join_i / t1 / done (EngineRequest::segment).
+struct LaunchEvents {
+  hipEvent_t ready = nullptr, t0 = nullptr, join_r = nullptr, join_i = nullptr, t1 = nullptr, done = nullptr;
+  unsigned* h_abort = nullptr;
+};
+
 // Queue one launch on a slot's stream pair: the roles stream waits for `ready` and (if given) for
-// `prev`, the items stream forks from it; `mine` is recorded at the end (the slot's busy mark).
-// r2: the request whose chains share the launch (p = split_plan(a, dev, &r2->a)); its own events are
+// `prev`, the items stream forks from it; roles_end is recorded behind the roles kernel (the items
+// stream waits for it: it may be e1.join_r), `mine` at the end (the slot's busy mark).
+// a2 / e2: the request whose chains share the launch (p = split_plan(a, dev, a2)); its own events are
 // recorded and its abort words copied beside the first request's.
-static void split_enqueue(const OdomArgs& a, SplitPlan& p, hipStream_t roles, hipStream_t items, hipEvent_t ready,
-                          hipEvent_t prev, hipEvent_t mine, hipEvent_t fork, hipEvent_t join_r, hipEvent_t join_i,
-                          hipEvent_t t0, hipEvent_t t1, unsigned* h_abort, hipEvent_t done,
-                          const EngineRequest* r2 = nullptr) {
+static void split_enqueue(const OdomArgs& a, SplitPlan& p, hipStream_t roles, hipStream_t items, hipEvent_t prev,
+                          hipEvent_t mine, hipEvent_t fork, hipEvent_t roles_end, const LaunchEvents& e1,
+                          const OdomArgs* a2 = nullptr, const LaunchEvents* e2 = nullptr) {
   EngCtl& ctl = p.ctl;
   ctl.gen = next_engine_gen();
-  (void)hipStreamWaitEvent(roles, ready, 0);
-  if (r2) (void)hipStreamWaitEvent(roles, r2->ready, 0);
+  if (e1.ready) (void)hipStreamWaitEvent(roles, e1.ready, 0);
+  if (a2 && e2->ready) (void)hipStreamWaitEvent(roles, e2->ready, 0);
   if (prev) (void)hipStreamWaitEvent(roles, prev, 0);
-  if (t0) (void)hipEventRecord(t0, roles);
-  if (r2 && r2->t0) (void)hipEventRecord(r2->t0, roles);
+  if (e1.t0) (void)hipEventRecord(e1.t0, roles);
+  if (a2 && e2->t0) (void)hipEventRecord(e2->t0, roles);
   // zero the control words of this launch, all but word 3 (the sticky abort)
   hipLaunchKernelGGL(k_eng_zero, dim3(1), dim3(256), 0, roles, ctl, (int)p.words);
   (void)hipEventRecord(fork, roles);
   (void)hipStreamWaitEvent(items, fork, 0);
-  if (r2) {
+  if (a2) {
     OdomArgs2 aa;
     aa.b[0] = a;
-    aa.b[1] = r2->a;
+    aa.b[1] = *a2;
     hipLaunchKernelGGL(k_odom_roles2, dim3(p.roles_grid), dim3(kEngThreads), 0, roles, aa, ctl);
     switch (ctl.qpw) {
       case 4: hipLaunchKernelGGL(k_odom_items2<4>, dim3(p.grid), dim3(64 * ctl.Q), 0, items, aa, ctl); break;
@@ -3579,22 +3603,23 @@ static void split_enqueue(const OdomArgs& a, SplitPlan& p, hipStream_t roles, hi
       default: hipLaunchKernelGGL(k_odom_items<1>, dim3(p.grid), dim3(64 * ctl.Q), 0, items, a, ctl); break;
     }
   }
-  (void)hipEventRecord(join_r, roles);
-  (void)hipEventRecord(join_i, items);
-  if (r2) {
-    (void)hipEventRecord(r2->join_r, roles);
-    (void)hipEventRecord(r2->join_i, items);
+  (void)hipEventRecord(roles_end, roles);
+  if (e1.join_r && e1.join_r != roles_end) (void)hipEventRecord(e1.join_r, roles);
+  if (e1.join_i) (void)hipEventRecord(e1.join_i, items);
+  if (a2) {
+    if (e2->join_r) (void)hipEventRecord(e2->join_r, roles);
+    if (e2->join_i) (void)hipEventRecord(e2->join_i, items);
   }
-  (void)hipStreamWaitEvent(items, join_r, 0);  // the device's engine ends when both kernels do
-  if (t1) (void)hipEventRecord(t1, items);
-  if (r2 && r2->t1) (void)hipEventRecord(r2->t1, items);
+  (void)hipStreamWaitEvent(items, roles_end, 0);  // the device's engine ends when both kernels do
+  if (e1.t1) (void)hipEventRecord(e1.t1, items);
+  if (a2 && e2->t1) (void)hipEventRecord(e2->t1, items);
   // the launch's error and sticky abort words to the host, and its end, before the slot's next
   // launch can queue behind it
-  if (h_abort) (void)hipMemcpyAsync(h_abort, a.eng_ctl + 2, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, items);
-  if (done) (void)hipEventRecord(done, items);
-  if (r2) {  // a give-up marks both batches: the launch's abort words are the first batch's
-    if (r2->h_abort) (void)hipMemcpyAsync(r2->h_abort, a.eng_ctl + 2, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, items);
-    if (r2->done) (void)hipEventRecord(r2->done, items);
+  if (e1.h_abort) (void)hipMemcpyAsync(e1.h_abort, a.eng_ctl + 2, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, items);
+  if (e1.done) (void)hipEventRecord(e1.done, items);
+  if (a2) {  // a give-up marks both batches: the launch's abort words are the first batch's
+    if (e2->h_abort) (void)hipMemcpyAsync(e2->h_abort, a.eng_ctl + 2, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, items);
+    if (e2->done) (void)hipEventRecord(e2->done, items);
   }
   (void)hipEventRecord(mine, items);
 }
@@ -3630,8 +3655,9 @@ int launch_odometry_chain_split(const OdomArgs& a, hipEvent_t ready, hipEvent_t 
   // its grid for `depth` engines, so it starts once theirs have ended
   for (int s = 0; s < EngineGate::kMaxDepth; s++)
     if (gate->slot_used[s]) (void)hipStreamWaitEvent(gate->roles[slot], gate->slot_ev[s], 0);
-  split_enqueue(a, p, gate->roles[slot], gate->items[slot], ready, prev, gate->ev[n % EngineGate::kMaxDepth], fork,
-                join_r, join_i, t0, t1, h_abort, done);
+  LaunchEvents e1;
+  e1.ready = ready; e1.t0 = t0; e1.join_r = join_r; e1.join_i = join_i; e1.t1 = t1; e1.done = done; e1.h_abort = h_abort;
+  split_enqueue(a, p, gate->roles[slot], gate->items[slot], prev, gate->ev[n % EngineGate::kMaxDepth], fork, join_r, e1);
   return p.grid;
 }
 
@@ -3639,7 +3665,8 @@ int launch_odometry_chain_split(const OdomArgs& a, hipEvent_t ready, hipEvent_t 
 // release_engine_streams.  Requests are launched in submission order among those whose `ready`
 // event has completed, each on a slot whose last launch has ended (slot_ev), while fewer than the
 // request's depth engines are in flight.  Two compatible requests go out as one launch (pairing,
-// below).  It polls every 20 us while something waits.
+// below), and a one-chain request may go out as several launches, a segment of its rounds each
+// (segments, below).  It polls every 20 us while something waits or a segment is in flight.
 bool engine_dispatch_enabled() {
   static const bool on = !(getenv("LISLAM_ENGINE_DISPATCH") && atoi(getenv("LISLAM_ENGINE_DISPATCH")) == 0);
   return on;
@@ -3655,7 +3682,45 @@ static bool pair_compatible(const EngineRequest* x, const EngineRequest* y) {
   return a.n_chains == 1 && b.n_chains == 1 && p.depth > 1 && p.depth == q.depth && !p.solo && !q.solo &&
          p.ctl.qpw == q.ctl.qpw && p.ctl.Q == q.ctl.Q && a.cap_sharp == b.cap_sharp && a.cap_flat == b.cap_flat &&
          a.cap_less_sharp == b.cap_less_sharp && a.H == b.H && a.max_iterations == b.max_iterations &&
-         a.eng_ctl != b.eng_ctl;
+         a.eng_ctl != b.eng_ctl && x->segment == y->segment;
+}
+
+// Segments.  A request with segment = L > 0 (one chain, submit_odometry_chain_split) goes out as
+// launches of L rounds, the last one shorter.  After each but the last the dispatcher keeps the
+// request (EngineGate::flying) and, once that launch's end event has completed and its abort words
+// read zero, puts it back in the queue as a continuation: ahead of every fresh request, the oldest
+// chain first, so no chain starves.  Continuations and fresh requests pair under pair_compatible
+// (the same L: both segments of a launch then run L rounds unless one is its chain's last, which
+// pair_of ends).  A chain that becomes ready while another runs thus waits for at most one segment
+// and shares every launch after it, and one whose partner ends early takes the next.
+// The rounds of x's next launch, and whether it is the chain's last.
+static int chain_rounds(const EngineRequest* x) { return min(x->a.chain_len, x->a.S - 1); }
+static int segment_rounds(const EngineRequest* x) {
+  const int left = chain_rounds(x) - x->next_round;
+  return x->segment > 0 ? min(x->segment, left) : left;
+}
+// The launch's arguments: from round next_round, starting from what the previous segment left.
+static OdomArgs segment_args(const EngineRequest* x) {
+  OdomArgs a = x->a;
+  a.r0 = x->next_round;
+  if (a.r0 > 0) a.init_state = a.resume;
+  if (x->next_round + segment_rounds(x) == chain_rounds(x)) a.resume = nullptr;  // the last: `state` holds the end
+  return a;
+}
+static LaunchEvents segment_events(const EngineRequest* x) {
+  LaunchEvents e;
+  e.ready = x->ready;
+  e.h_abort = x->h_abort;
+  if (x->next_round == 0) e.t0 = x->t0;
+  if (x->next_round + segment_rounds(x) == chain_rounds(x)) {
+    e.join_r = x->join_r; e.join_i = x->join_i; e.t1 = x->t1; e.done = x->done;
+  }
+  return e;
+}
+// A plan for R rounds: 8 + 4 R control words for one or two chains at most.
+static void plan_rounds(SplitPlan& p, int R) {
+  p.ctl.R = R;
+  p.words = ((size_t)6 + p.ctl.C + (size_t)2 * R * p.ctl.C + 3) / 4 * 4;
 }
 // How long (us) a lone ready request is held for a compatible request that is queued but whose
 // inputs do not exist yet, while another engine runs (pairing auto).  0: pair only what is ready
@@ -3672,7 +3737,7 @@ static void dispatcher_loop(EngineGate* g, int dev) {
   (void)hipSetDevice(dev);
   std::unique_lock<std::mutex> lk(g->mu);
   for (;;) {
-    if (g->q.empty()) {
+    if (g->q.empty() && g->flying.empty()) {  // (a stop drains the continuations too)
       if (g->stop) break;
       g->cv_req.wait(lk);
       continue;
@@ -3681,11 +3746,48 @@ static void dispatcher_loop(EngineGate* g, int dev) {
     // sized for: nothing is dispatched beside it
     bool gated = false;
     for (hipEvent_t e : g->ev) gated = gated || (e && hipEventQuery(e) != hipSuccess);
-    bool running[EngineGate::kMaxDepth];
+    bool running[EngineGate::kMaxDepth], broken[EngineGate::kMaxDepth];
     int busy = gated ? EngineGate::kMaxDepth : 0;
     for (int s = 0; s < EngineGate::kMaxDepth; s++) {
-      running[s] = g->slot_used[s] && hipEventQuery(g->slot_ev[s]) != hipSuccess;
+      const hipError_t e = g->slot_used[s] ? hipEventQuery(g->slot_ev[s]) : hipSuccess;
+      running[s] = e != hipSuccess;
+      broken[s] = e != hipSuccess && e != hipErrorNotReady;  // the device has failed: it will never be ready
       busy += running[s];
+    }
+    // Segments whose launch has ended (by the same poll that frees its slot, so the slot cannot
+    // have been taken again): back into the queue, continuations first and the oldest chain first;
+    // a give-up (or a failed device, which is not polled for ever) ends the chain there.
+    for (size_t i = 0; i < g->flying.size();) {
+      EngineRequest* x = g->flying[i];
+      const int s = x->seg_slot;
+      if (running[s] && !broken[s]) { i++; continue; }
+      g->flying.erase(g->flying.begin() + i);
+      x->seg_slot = -1;
+      if (broken[s] && x->h_abort) { x->h_abort[0] = 0xffu; x->h_abort[1] = 1u; }
+      if (broken[s] || (x->h_abort && x->h_abort[1] != 0)) {
+        // the batch's events as its last segment would have recorded them, behind the launch that
+        // gave up; engine_settle reads h_abort and re-runs the whole chain on the per-round schedule
+        (void)hipEventRecord(x->join_r, g->roles[s]);
+        (void)hipEventRecord(x->join_i, g->items[s]);
+        if (x->t1) (void)hipEventRecord(x->t1, g->items[s]);
+        if (x->done) (void)hipEventRecord(x->done, g->items[s]);
+        (void)hipGetLastError();
+        delete static_cast<SplitPlan*>(x->plan);
+        x->plan = nullptr;
+        x->state.store(2);
+        g->cv_launched.notify_all();
+        continue;
+      }
+      size_t at = 0;
+      while (at < g->q.size() && g->q[at]->next_round > 0 && g->q[at]->seq < x->seq) at++;
+      g->q.insert(g->q.begin() + at, x);
+    }
+    if (g->q.empty()) {  // only segments in flight: poll for their end
+      (void)hipGetLastError();
+      lk.unlock();
+      std::this_thread::sleep_for(std::chrono::microseconds(20));
+      lk.lock();
+      continue;
     }
     // the first ready request in submission order takes a free slot, with a ready compatible
     // partner if there is one.  A request held for its partner keeps a free slot to itself
@@ -3709,12 +3811,26 @@ static void dispatcher_loop(EngineGate* g, int dev) {
         if (hipEventQuery(g->q[j]->ready) == hipSuccess) y = g->q[j];
         else coming = true;
       }
+      // ... or whose segment in flight, a launch of its own, ends within a segment's time (one that
+      // shares its launch comes back with its partner: waiting for the two would leave one over)
+      bool flying = false;
+      for (size_t j = 0; j < g->flying.size() && !y && !flying; j++)
+        flying = !g->flying[j]->seg_shared && pair_compatible(x, g->flying[j]);
       if (!y && !g->stop) {
-        // require: until a partner is ready, within the engine's wait bound (ticks of 10 ns);
-        // auto: only while another engine runs and a partner is on its way, for pair_hold_us
+        // require: until a partner is ready, within the engine's wait bound (ticks of 10 ns); a
+        // continuation only while a partner is on its way (its partner's chain may have ended:
+        // nothing says another will come);
+        // auto: only while another engine runs and a partner is on its way, for pair_hold_us; for a
+        // partner in flight until its launch ends (at most a segment, once: from then on the two
+        // end together.  A hold shorter than a segment would expire at every boundary instead, the
+        // two chains taking turns to wait for each other and never meeting)
         long bound_us = -1;
-        if (x->pairing == kPairRequire && x->a.n_chains == 1 && px.depth > 1) bound_us = (long)(px.ctl.wait_ticks / 100ull);
-        else if (x->pairing == kPairAuto && coming && busy > 0) bound_us = kPairHoldUs;
+        const long wait_us = (long)(px.ctl.wait_ticks / 100ull);
+        if (x->pairing == kPairRequire && x->a.n_chains == 1 && px.depth > 1) {
+          if (x->next_round == 0 || coming || flying) bound_us = wait_us;
+        } else if (x->pairing == kPairAuto && busy > 0 && kPairHoldUs > 0) {
+          bound_us = flying ? wait_us : coming ? kPairHoldUs : -1;
+        }
         // the bound runs from the first poll at which the request could have gone out alone and
         // was kept back; a hold whose condition lapses is forgotten (the next one starts afresh)
         if (bound_us > 0) {
@@ -3733,10 +3849,16 @@ static void dispatcher_loop(EngineGate* g, int dev) {
     }
     if (r) {
       if (!g->slot_ev[free_slot]) (void)hipEventCreateWithFlags(&g->slot_ev[free_slot], hipEventDisableTiming);
+      if (!g->slot_jr[free_slot]) (void)hipEventCreateWithFlags(&g->slot_jr[free_slot], hipEventDisableTiming);
       if (r2 && r2->ctl_words > r->ctl_words) std::swap(r, r2);  // the control words: the larger allocation
+      // this launch: the requests' next segments (the whole chains when they are not segmented)
+      const OdomArgs a1 = segment_args(r);
+      OdomArgs a2{};
       SplitPlan pair;
       if (r2) {
-        pair = split_plan(r->a, dev, &r2->a);
+        a2 = segment_args(r2);
+        pair = split_plan(a1, dev, &a2);
+        plan_rounds(pair, max(segment_rounds(r), segment_rounds(r2)));  // the shorter one ends early (pair_of)
         // 8 + 4 R control words (R <= the longer batch's S - 1) against the larger allocation's
         // 8 + 10 S: they fit.  A build without asserts launches the two unpaired and says so.
         assert(pair.words <= r->ctl_words);
@@ -3746,9 +3868,12 @@ static void dispatcher_loop(EngineGate* g, int dev) {
           r2 = nullptr;
         }
       }
-      SplitPlan& p = r2 ? pair : *static_cast<SplitPlan*>(r->plan);
-      split_enqueue(r->a, p, g->roles[free_slot], g->items[free_slot], r->ready, nullptr, g->slot_ev[free_slot],
-                    r->fork, r->join_r, r->join_i, r->t0, r->t1, r->h_abort, r->done, r2);
+      SplitPlan one = *static_cast<SplitPlan*>(r->plan);
+      plan_rounds(one, segment_rounds(r));
+      SplitPlan& p = r2 ? pair : one;
+      const LaunchEvents e1 = segment_events(r), e2 = r2 ? segment_events(r2) : LaunchEvents{};
+      split_enqueue(a1, p, g->roles[free_slot], g->items[free_slot], nullptr, g->slot_ev[free_slot], r->fork,
+                    e1.join_r ? e1.join_r : g->slot_jr[free_slot], e1, r2 ? &a2 : nullptr, r2 ? &e2 : nullptr);
       g->slot_used[free_slot] = true;
 #if LISLAM_ENG_STAMPS
       fprintf(stderr, "dispatch gen %u slot %d at %.3f ms (queued %zu, busy %d, paired %d)\n", p.ctl.gen, free_slot,
@@ -3758,10 +3883,17 @@ static void dispatcher_loop(EngineGate* g, int dev) {
       for (EngineRequest* x : {r, r2}) {
         if (!x) continue;
         g->q.erase(std::find(g->q.begin(), g->q.end(), x));
+        x->paired = x->paired || r2 != nullptr;  // (false when submitted)
+        x->held = false;
+        x->next_round += segment_rounds(x);
+        if (x->next_round < chain_rounds(x)) {  // more segments: kept until this launch has ended
+          x->seg_slot = free_slot;
+          x->seg_shared = r2 != nullptr;
+          g->flying.push_back(x);
+          continue;
+        }
         delete static_cast<SplitPlan*>(x->plan);
         x->plan = nullptr;
-        x->paired = r2 != nullptr;
-        x->held = false;
         x->state.store(2);
       }
       g->cv_launched.notify_all();
@@ -3806,6 +3938,13 @@ int submit_odometry_chain_split(EngineRequest* r) {
     g->th = new std::thread(dispatcher_loop, g, dev);
   }
   r->plan = new SplitPlan(split_plan(r->a, dev));
+  // segments: one chain with somewhere to leave its state (its resume rows are init_state's)
+  if (r->a.n_chains != 1 || !r->a.resume || r->segment < 0) r->segment = 0;
+  if (r->segment == 0) r->a.resume = nullptr;
+  r->a.r0 = 0;
+  r->next_round = 0;
+  r->seg_slot = -1;
+  r->seq = g->submits++;
   r->state.store(1);
   g->q.push_back(r);
   g->cv_req.notify_one();

@@ -69,6 +69,12 @@ class Context:
         holds a lone request for a partner (deterministic pairs: tests).  Results are the same."""
         nat.check(self.lib.lislam_set_engine_pairing(self.h, int(mode)), self.h, "lislam_set_engine_pairing")
 
+    def set_engine_segment(self, pairs: int):
+        """lislam_set_engine_segment: at depth > 1 a one-chain odometry call runs as engine launches of
+        `pairs` scan pairs each, and the dispatcher chooses the chain's partner anew for every launch;
+        0 = whole chains.  A new context starts from the library's build default.  Results are the same."""
+        nat.check(self.lib.lislam_set_engine_segment(self.h, int(pairs)), self.h, "lislam_set_engine_segment")
+
     DISTORTION_OFF, DISTORTION_QUERIES, DISTORTION_TO_END = 0, 1, 2  # lislam_set_distortion
 
     def set_distortion(self, mode: int):
