@@ -39,7 +39,9 @@
  *                             <- pcl::fromROSMsg / toROSMsg            src/image_handler.h_ouster:105-106,
  *                                                                      src/scanRegistration.cpp:592-642
  *   lislam_loop_icp           <- loopClosureThread's USE_ICP block     src/intensity_feature_tracker.cpp:217-366
- *   lislam_odom_fuse          <- odomHandler callback                 src/odom_handler_node.cpp:44-132
+ *   lislam_keyframes_* / lislam_loop_verify
+ *                             <- keyframe_pool_[i].cloud_track_ + the same block for a batch of candidates
+ *   lislam_odom_fuse          <- odomHandler callback                src/odom_handler_node.cpp:44-132
  *   lislam_place_*            <- SCManager (Scan Context)             src/Scancontext.cpp:126-344
  *   lislam_bow_*              <- detectLoop's DBoW3 query (ORB words)  src/loop_closure_handler.cpp:127-188
  *   lislam_bow_train(er_*)    <- DBoW3::Vocabulary::create: the tree    src/loop_closure_handler.cpp:12-17 loads from a file
@@ -532,6 +534,39 @@ typedef struct {
 int lislam_loop_icp(lislam_ctx* ctx, const lislam_icp_config* cfg, const float* cur, int32_t n_cur, const double* T_cur,
                     const float* hist, const int32_t* hist_counts, int32_t n_hist, const double* T_hist, double* T_icp,
                     double* T_cur2map, double* fitness, int32_t* info);
+/* loopClosureProcessor_.keyframe_pool_[i].cloud_track_ as a device-resident pool: keyframe ids are
+ * consecutive from 0 in the order added (keyframeId_).  capacity = the most keyframes, point_capacity
+ * the most points (x, y, z, intensity) it holds; going over either is LISLAM_ERR_CAPACITY and adds
+ * nothing.  A cloud of 0 points is a valid keyframe. */
+typedef struct lislam_keyframes lislam_keyframes;
+int lislam_keyframes_create(lislam_ctx* ctx, int32_t capacity, int64_t point_capacity, lislam_keyframes** out);
+int lislam_keyframes_destroy(lislam_keyframes* kf);
+int lislam_keyframes_size(lislam_keyframes* kf, int32_t* n_keyframes, int64_t* n_points);
+/* n_clouds clouds: points = their float quadruples one cloud after the other (host or device
+ * memory), counts[n_clouds] (host) their sizes. */
+int lislam_keyframes_add_clouds(lislam_keyframes* kf, const void* points, const int32_t* counts, int32_t n_clouds);
+/* cloud_track of scans [first_scan, first_scan + n_scans) of an extracted batch of the same context
+ * (want_images = 1), copied device to device; preconditions and error codes as lislam_place_add_batch. */
+int lislam_keyframes_add_batch(lislam_keyframes* kf, lislam_batch* b, int32_t first_scan, int32_t n_scans);
+/* Keyframe index into dst (cap_points quadruples, host); *n (nullable) = its points. */
+int lislam_keyframes_download(lislam_keyframes* kf, int32_t index, float* dst, int32_t cap_points, int32_t* n);
+/* lislam_loop_icp for n_loops candidates in one set of launches, the clouds read from the pool.
+ * Candidate k = (cur_id[k], loop_id[k]) (host arrays); T_kf[pool size][16] = getTransformMatrix(i)
+ * of every keyframe, row-major (host or device memory).  The submap (getSubmapOfhistory, :174-193)
+ * is the keyframes i in [max(0, loop - submap_window), loop + submap_window] with i <= cur (the
+ * reference's i < keyframe_pool_.size() when cur was the newest), ascending, each under T_kf[i];
+ * submap_window in 0..4 (the reference compiles 1).  Row k of T_icp[n][16], T_cur2map[n][16],
+ * fitness[n], info[n][8] (host, each nullable) is exactly what
+ *   lislam_loop_icp(ctx, cfg, pool[cur], n, T_kf[cur], submap clouds, counts, n_hist, their T_kf rows, ...)
+ * returns, bit for bit.  loop_id[k] < 0 (the "no loop" of lislam_place_detect / lislam_bow_detect)
+ * gives info[0] = -3, T_icp = identity, T_cur2map = T_kf[cur], fitness = DBL_MAX, the other info
+ * fields 0.  cur_id out of range, loop_id >= pool size, loop_id > cur_id or submap_window out of
+ * range: LISLAM_ERR_ARG with a lislam_last_error text, nothing computed, outputs untouched.  More
+ * than 0x3fffffff raw points over all candidates: LISLAM_ERR_CAPACITY.  n_loops == 0 is a no-op.
+ * The same keyframe may appear in any number of candidates. */
+int lislam_loop_verify(lislam_keyframes* kf, const lislam_icp_config* cfg, int32_t submap_window, const int32_t* cur_id,
+                       const int32_t* loop_id, int32_t n_loops, const double* T_kf, double* T_icp, double* T_cur2map,
+                       double* fitness, int32_t* info);
 /* odomHandler's callback (src/odom_handler_node.cpp:44-132) over n synchronized pairs in order:
  * aloam[n][7] = /laser_odom_to_init_aloam, intensity[n][7] = /laser_odom_to_init_intensity
  * (q x,y,z,w, t), skip[n] = 1 when the intensity message's child_frame_id is "/odom_skip";

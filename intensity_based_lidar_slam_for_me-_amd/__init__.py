@@ -4,11 +4,12 @@ Import with ``importlib.import_module("intensity_based_lidar_slam_for_me-_amd")`
 name is not a Python identifier).  The compute path is the HIP library ``liblislam.so`` built by
 ``__graft_entry__.build()``; there is no CPU fallback.
 """
-from . import bow, intensity, loop, mapping, native, place, posegraph, synth  # noqa: F401
+from . import bow, intensity, keyframes, loop, mapping, native, place, posegraph, synth  # noqa: F401
 from .bow import BowDatabase, BowTrainer, Vocabulary  # noqa: F401
+from .keyframes import KeyframePool, close_loops  # noqa: F401
 from .place import ScanContext  # noqa: F401
 from .posegraph import PoseGraph  # noqa: F401
 from .frontend import Batch, Context, Features, ImageHandler, LaserOdometry, ScanRegistration, eval_factors  # noqa: F401
 
-__all__ = ["bow", "intensity", "loop", "mapping", "native", "place", "posegraph", "synth", "Batch", "BowDatabase", "BowTrainer", "Context", "Features", "ImageHandler", "LaserOdometry",
-           "PoseGraph", "ScanContext", "ScanRegistration", "Vocabulary", "eval_factors"]
+__all__ = ["bow", "intensity", "keyframes", "loop", "mapping", "native", "place", "posegraph", "synth", "Batch", "BowDatabase", "BowTrainer", "Context", "Features", "ImageHandler", "KeyframePool", "LaserOdometry",
+           "PoseGraph", "ScanContext", "ScanRegistration", "Vocabulary", "close_loops", "eval_factors"]

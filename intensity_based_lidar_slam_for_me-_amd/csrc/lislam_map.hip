@@ -33,6 +33,7 @@
 #include <vector>
 
 #include "lislam_prims.hpp"
+#include "lislam_batch.hpp"
 #include "lislam_ctx.hpp"
 #include "lislam_device.hpp"
 #include "lislam_lm.hpp"
@@ -360,19 +361,11 @@ __device__ __forceinline__ void knn_pass(const MapView& m, const float4& q, int 
   }
 }
 
-// queries: n points of `stride` floats (optionally counted on the device: *qcount); pose
-// (device, nullable): queries are sensor-frame points mapped by pointAssociateToMap first.
+// The search of one query q by its group of G lanes: the k best of m into row qi of the outputs.
 template <int K, int G>
-__global__ __launch_bounds__(256) void k_knn(MapView m, const float* queries, int stride, const int* qcount, int nq,
-                                             const double* pose, int k, float max_d2, float4* out_pts, float* out_d2,
-                                             int* out_found) {
-  const int qi = xcd_block(blockIdx.x, gridDim.x) * (256 / G) + (int)(threadIdx.x / G);
+__device__ __forceinline__ void knn_query(const MapView& m, const float4 q, int qi, int k, float max_d2, float4* out_pts,
+                                          float* out_d2, int* out_found) {
   const int lane = threadIdx.x & (G - 1);
-  const int n = qcount ? min(*qcount, nq) : nq;
-  if (qi >= n) return;  // whole groups leave
-  const float* qp = queries + (size_t)qi * stride;
-  float4 q = make_float4(qp[0], qp[1], qp[2], 0.f);
-  if (pose) q = to_world(pose, q.x, q.y, q.z);
   const int cx = cell_of(q.x, m.inv_cell), cy = cell_of(q.y, m.inv_cell), cz = cell_of(q.z, m.inv_cell);
   KBest<K> b, mg;
   kb_clear(b);
@@ -422,6 +415,21 @@ __global__ __launch_bounds__(256) void k_knn(MapView m, const float* queries, in
     if (out_d2) out_d2[(size_t)qi * k + r] = mg.d[r];
   }
   if (out_found && lane == 0) out_found[qi] = found;
+}
+
+// queries: n points of `stride` floats (optionally counted on the device: *qcount); pose
+// (device, nullable): queries are sensor-frame points mapped by pointAssociateToMap first.
+template <int K, int G>
+__global__ __launch_bounds__(256) void k_knn(MapView m, const float* queries, int stride, const int* qcount, int nq,
+                                             const double* pose, int k, float max_d2, float4* out_pts, float* out_d2,
+                                             int* out_found) {
+  const int qi = xcd_block(blockIdx.x, gridDim.x) * (256 / G) + (int)(threadIdx.x / G);
+  const int n = qcount ? min(*qcount, nq) : nq;
+  if (qi >= n) return;  // whole groups leave
+  const float* qp = queries + (size_t)qi * stride;
+  float4 q = make_float4(qp[0], qp[1], qp[2], 0.f);
+  if (pose) q = to_world(pose, q.x, q.y, q.z);
+  knn_query<K, G>(m, q, qi, k, max_d2, out_pts, out_d2, out_found);
 }
 
 // ------------------------------------------------------------------ fits (fp64, one thread per query)
@@ -1261,13 +1269,16 @@ uint32_t pow2_at_least(uint64_t v) {
 
 }  // namespace
 
-struct LoopState;  // lislam_loop_icp's target map and buffers (end of file)
+struct LoopState;    // lislam_loop_icp's target map and buffers (end of file)
+struct VerifyState;  // lislam_loop_verify's buffers (end of file)
+static void free_verify_state(VerifyState* v);
 
 // Scratch shared by the stateless entry points of a context (voxel grid, solve, association).
 struct MapScratch {
   DBuf sort_tmp, keys32a, keys32b, idxa, idxb, flag, pos, vin, vout, bounds, counters;
   DBuf lm, partial, rec, kind, x, nb, d2, found, q, vox, qc, qs;
   LoopState* loop = nullptr;
+  VerifyState* verify = nullptr;
 };
 
 struct lislam_map {
@@ -2546,9 +2557,9 @@ __device__ __forceinline__ void tree_sum(double (*red)[kRed]) {
   }
 }
 
-__global__ __launch_bounds__(kRed) void k_lc_step(IcpDev* st, const float4* src, const float4* nb, const float* d2,
-                                                  const int* found, int n, IcpParams P) {
-  __shared__ double red[9][kRed];
+// One ICP iteration of one source cloud by a whole 1024-thread workgroup (red: its LDS)
+__device__ __forceinline__ void lc_step_body(IcpDev* st, const float4* src, const float4* nb, const float* d2,
+                                             const int* found, int n, const IcpParams& P, double (*red)[kRed]) {
   const int t = threadIdx.x;
   if (st->done) {
     if (t == 0) st->run = 0;
@@ -2633,28 +2644,34 @@ __global__ __launch_bounds__(kRed) void k_lc_step(IcpDev* st, const float4* src,
   }
 }
 
+__global__ __launch_bounds__(kRed) void k_lc_step(IcpDev* st, const float4* src, const float4* nb, const float* d2,
+                                                  const int* found, int n, IcpParams P) {
+  __shared__ double red[9][kRed];
+  lc_step_body(st, src, nb, d2, found, n, P, red);
+}
+
+// transformPointCloud with a float Matrix4f (row-major T)
+__device__ __forceinline__ float4 lc_tf_f(const float* T, const float4 p) {
+  return make_float4(((T[0] * p.x + T[1] * p.y) + T[2] * p.z) + T[3], ((T[4] * p.x + T[5] * p.y) + T[6] * p.z) + T[7],
+                     ((T[8] * p.x + T[9] * p.y) + T[10] * p.z) + T[11], p.w);
+}
+
 // source *= T of this iteration (skipped when k_lc_step did not run)
 __global__ void k_lc_apply(const IcpDev* st, float4* src, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n || !st->run) return;
-  const float* T = st->T;
-  const float4 p = src[i];
-  src[i] = make_float4(((T[0] * p.x + T[1] * p.y) + T[2] * p.z) + T[3], ((T[4] * p.x + T[5] * p.y) + T[6] * p.z) + T[7],
-                       ((T[8] * p.x + T[9] * p.y) + T[10] * p.z) + T[11], p.w);
+  src[i] = lc_tf_f(st->T, src[i]);
 }
 
 // getFitnessScore's transformPointCloud(*input_, final_transformation_)
 __global__ void k_lc_final_tf(const IcpDev* st, const float4* src, int n, float4* out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const float* T = st->F;
-  const float4 p = src[i];
-  out[i] = make_float4(((T[0] * p.x + T[1] * p.y) + T[2] * p.z) + T[3], ((T[4] * p.x + T[5] * p.y) + T[6] * p.z) + T[7],
-                       ((T[8] * p.x + T[9] * p.y) + T[10] * p.z) + T[11], p.w);
+  out[i] = lc_tf_f(st->F, src[i]);
 }
 
-__global__ __launch_bounds__(kRed) void k_lc_fitness(IcpDev* st, const float* d2, const int* found, int n) {
-  __shared__ double red[2][kRed];
+// getFitnessScore of one source cloud by a whole 1024-thread workgroup (red: its LDS)
+__device__ __forceinline__ void lc_fitness_body(IcpDev* st, const float* d2, const int* found, int n, double (*red)[kRed]) {
   const int t = threadIdx.x;
   double a0 = 0, a1 = 0;
   for (int i = t; i < n; i += kRed) {
@@ -2667,6 +2684,11 @@ __global__ __launch_bounds__(kRed) void k_lc_fitness(IcpDev* st, const float* d2
   __syncthreads();
   tree_sum<2>(red);
   if (t == 0) st->fitness = red[0][0] > 0 ? red[1][0] / red[0][0] : DBL_MAX;
+}
+
+__global__ __launch_bounds__(kRed) void k_lc_fitness(IcpDev* st, const float* d2, const int* found, int n) {
+  __shared__ double red[2][kRed];
+  lc_fitness_body(st, d2, found, n, red);
 }
 
 }  // namespace loopk
@@ -2685,6 +2707,7 @@ struct LoopState {
 void lislam_free_map_scratch(void* p) {
   auto* s = static_cast<MapScratch*>(p);
   delete s->loop;
+  free_verify_state(s->verify);
   delete s;
 }
 
@@ -2854,6 +2877,761 @@ int lislam_loop_icp(lislam_ctx* c, const lislam_icp_config* cfg, const float* cu
       Tc[4 * r + col] = ((Ti[4 * r] * T_cur[col] + Ti[4 * r + 1] * T_cur[4 + col]) + Ti[4 * r + 2] * T_cur[8 + col]) +
                         Ti[4 * r + 3] * T_cur[12 + col];
   return finish();
+}
+
+}  // extern "C"
+
+// ================================================================== keyframe pool + batched loop verification
+// lislam_keyframes is loopClosureProcessor_.keyframe_pool_[i].cloud_track_ in HBM: one float4 array,
+// keyframe i at [off[i], off[i + 1]) (the offsets live on the host).  lislam_loop_verify runs the
+// USE_ICP block above for L candidates with one set of launches.  A segment is one cloud of one
+// candidate: segment 2k the source (keyframe cur under T_kf[cur]), segment 2k + 1 the target (the
+// getSubmapOfhistory keyframes under their poses, concatenated).
+//   k_lv_transform  k_lc_tf_d's expression + k_lc_flags' test over every (candidate, keyframe)
+//                   piece, read from the pool in place, written as [src_0 | tgt_0 | src_1 | ...]
+//   select          exclusive sum of the flags + k_lv_compact (stable); segment counts from the sum
+//   VoxelGrid       per-segment bounds / min_b / div_b (k_lv_bounds), keys (segment << 32 | voxel
+//                   index) in one stable radix sort, runs summed in sorted order (k_lv_centroids).  A
+//                   segment whose index space overflows 2^31 - 1 gets its points' own positions as
+//                   keys: one-point runs in input order, p / 1.0f = p, i.e. it passes unchanged.
+//   target index    cell keys of every target, sorted by cell then (stable) by candidate; one point
+//                   array, one slice of the cell table and one MapView per candidate
+//   iterations      k_lv_knn (knn_query with the query's own view) -> k_lv_step (lc_step_body, one
+//                   1024-thread workgroup per candidate) -> k_lv_apply; a candidate that is done
+//                   drops out of all three.  The host reads the candidates' states once per chunk.
+// Per candidate every floating-point operation is lislam_loop_icp's, in its order: the results are
+// bit-identical to L single calls.
+namespace lislam {
+namespace loopk {
+
+struct LvPiece {   // one keyframe cloud of one segment
+  long long src;   // its first point in the pool
+  int dst, n;      // its first point in the concatenation, its points
+  int trow, seg;   // its row of T_kf, its segment
+};
+
+struct LvVox {  // VoxelGrid parameters of one segment
+  int min_b[3], mul1, mul2, overflow;
+};
+
+struct LvCand {          // a candidate that iterates
+  int w_off, ns;         // its source in the work arrays
+  int t_off, nt;         // its target in the index's point array
+  int src_vox, tgt_vox;  // where the two lie in the prepared concatenation
+  int h_off;             // its slice of the cell table
+  uint32_t hmask;
+};
+
+// the last j in [0, n) with off[j] <= i (off ascending, off[0] <= i)
+__device__ __forceinline__ int lv_find(const int* off, int n, int i) {
+  int lo = 0, hi = n - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (off[mid] <= i) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo;
+}
+
+__global__ void k_lv_transform(const float4* pool, const LvPiece* pc, const int* pdst, int np, const double* T, int ntot,
+                               int use_crop, float lo, float hi, float4* out, int* flag, int* seg) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= ntot) return;
+  const LvPiece P = pc[lv_find(pdst, np, i)];
+  const float4 p = pool[P.src + (i - P.dst)];
+  const double x = p.x, y = p.y, z = p.z;
+  const double* m = T + 16 * (size_t)P.trow;
+  const float4 o = make_float4((float)(((m[0] * x + m[1] * y) + m[2] * z) + m[3]), (float)(((m[4] * x + m[5] * y) + m[6] * z) + m[7]),
+                               (float)(((m[8] * x + m[9] * y) + m[10] * z) + m[11]), p.w);
+  bool keep = isfinite(o.x) && isfinite(o.y) && isfinite(o.z);
+  if (keep && use_crop) keep = !(o.x < lo || o.y < lo || o.z < lo || o.x > hi || o.y > hi || o.z > hi);
+  out[i] = o;
+  flag[i] = keep ? 1 : 0;
+  seg[i] = P.seg;
+}
+
+__global__ void k_lv_compact(const float4* in, const int* flag, const int* pos, const int* seg, int n, float4* out,
+                             int* oseg) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n || !flag[i]) return;
+  out[pos[i]] = in[i];
+  oseg[pos[i]] = seg[i];
+}
+
+// out[j] = the number of flagged elements before at[j] (at[j] == n: all of them)
+__global__ void k_lv_offsets(const int* pos, const int* flag, const int* at, int nat, int n, int* out) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= nat) return;
+  const int r = at[j];
+  out[j] = r < n ? pos[r] : pos[n - 1] + flag[n - 1];
+}
+
+// k_vg_bounds + the head of k_vg_keys, one workgroup per segment
+__global__ __launch_bounds__(1024) void k_lv_bounds(const float4* in, const int* off, float inv, LvVox* vx) {
+  __shared__ unsigned smn[3][16], smx[3][16];
+  const int s = blockIdx.x, b = off[s], e = off[s + 1];
+  if (b >= e) return;
+  unsigned mn[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, mx[3] = {0, 0, 0};
+  for (int i = b + (int)threadIdx.x; i < e; i += blockDim.x) {
+    const float4 p = in[i];
+    const unsigned c[3] = {mapk::ord_f(p.x), mapk::ord_f(p.y), mapk::ord_f(p.z)};
+    for (int k = 0; k < 3; k++) { mn[k] = min(mn[k], c[k]); mx[k] = max(mx[k], c[k]); }
+  }
+  for (int o = 32; o > 0; o >>= 1)
+    for (int k = 0; k < 3; k++) { mn[k] = min(mn[k], (unsigned)__shfl_xor((int)mn[k], o)); mx[k] = max(mx[k], (unsigned)__shfl_xor((int)mx[k], o)); }
+  const int w = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0)
+    for (int k = 0; k < 3; k++) { smn[k][w] = mn[k]; smx[k][w] = mx[k]; }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  float lo[3], hi[3];
+  for (int k = 0; k < 3; k++) {
+    unsigned a0 = smn[k][0], a1 = smx[k][0];
+    for (int j = 1; j < 16; j++) { a0 = min(a0, smn[k][j]); a1 = max(a1, smx[k][j]); }
+    lo[k] = mapk::unord_f(a0);
+    hi[k] = mapk::unord_f(a1);
+  }
+  const int64_t dx = (int64_t)((hi[0] - lo[0]) * inv) + 1, dy = (int64_t)((hi[1] - lo[1]) * inv) + 1,
+                dz = (int64_t)((hi[2] - lo[2]) * inv) + 1;
+  LvVox V;
+  V.overflow = dx * dy * dz > (int64_t)0x7fffffff ? 1 : 0;
+  int div_b[3];
+  for (int k = 0; k < 3; k++) {
+    V.min_b[k] = (int)floorf(lo[k] * inv);
+    div_b[k] = (int)floorf(hi[k] * inv) - V.min_b[k] + 1;
+  }
+  V.mul1 = div_b[0];
+  V.mul2 = div_b[0] * div_b[1];
+  vx[s] = V;
+}
+
+__global__ void k_lv_keys(const float4* in, const int* seg, const int* off, const LvVox* vx, float inv, int n,
+                          uint64_t* keys, int* idx) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int s = seg[i];
+  const LvVox V = vx[s];
+  uint32_t v;
+  if (V.overflow) {
+    v = (uint32_t)(i - off[s]);
+  } else {
+    const float4 p = in[i];
+    const int i0 = (int)(floorf(p.x * inv) - (float)V.min_b[0]);
+    const int i1 = (int)(floorf(p.y * inv) - (float)V.min_b[1]);
+    const int i2 = (int)(floorf(p.z * inv) - (float)V.min_b[2]);
+    v = (uint32_t)(i0 + i1 * V.mul1 + i2 * V.mul2);
+  }
+  keys[i] = ((uint64_t)(uint32_t)s << 32) | v;
+  idx[i] = i;
+}
+
+__global__ void k_lv_runs(const uint64_t* skeys, int n, int* flag) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) flag[i] = (i == 0 || skeys[i] != skeys[i - 1]) ? 1 : 0;
+}
+
+// k_vg_centroids over the (segment, voxel) runs
+__global__ void k_lv_centroids(const float4* in, const uint64_t* skeys, const int* sidx, const int* pos, const int* flag,
+                               int n, float4* out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n || !flag[i]) return;
+  const uint64_t key = skeys[i];
+  float4 c = in[sidx[i]];
+  int e = i + 1;
+  constexpr int U = 16;
+  int cntn = 1;
+  bool more = true;
+  while (more) {
+    int ix[U];
+#pragma unroll
+    for (int u = 0; u < U; u++) ix[u] = (e + u < n && skeys[e + u] == key) ? sidx[e + u] : -1;
+    float4 p[U];
+#pragma unroll
+    for (int u = 0; u < U; u++) p[u] = ix[u] >= 0 ? in[ix[u]] : make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+      if (ix[u] >= 0) {
+        c.x += p[u].x; c.y += p[u].y; c.z += p[u].z; c.w += p[u].w;
+        cntn++;
+      }
+    }
+    more = ix[U - 1] >= 0;
+    e += U;
+  }
+  const float cnt = (float)cntn;
+  c.x /= cnt; c.y /= cnt; c.z /= cnt; c.w /= cnt;
+  out[pos[i]] = c;
+}
+
+// the iterating candidates' sources, one after the other: the moving copy, the original, the owner
+__global__ void k_lv_src(const float4* vox, const LvCand* cd, const int* woff, int na, int n, float4* src, float4* src0,
+                         int* qseg) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int a = lv_find(woff, na, i);
+  const float4 p = vox[cd[a].src_vox + (i - woff[a])];
+  src[i] = p;
+  src0[i] = p;
+  qseg[i] = a;
+}
+
+// their targets: w = index within the target (k_lc_ids), cell key (k_cell_keys)
+__global__ void k_lv_tgt(const float4* vox, const LvCand* cd, const int* toff, int na, int n, float inv, float4* tp,
+                         uint64_t* keys, int* idx) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int a = lv_find(toff, na, i), local = i - toff[a];
+  const float4 p = vox[cd[a].tgt_vox + local];
+  tp[i] = make_float4(p.x, p.y, p.z, __int_as_float(local));
+  keys[i] = mapk::pack_cell(mapk::cell_of(p.x, inv), mapk::cell_of(p.y, inv), mapk::cell_of(p.z, inv));
+  idx[i] = i;
+}
+
+__global__ void k_lv_owner(const int* idx, const int* toff, int na, int n, uint32_t* owner) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j < n) owner[j] = (uint32_t)lv_find(toff, na, idx[j]);
+}
+
+__global__ void k_lv_tgather(const float4* tp, const int* perm, int n, float inv, float4* pts, uint64_t* ckey) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  const float4 p = tp[perm[j]];
+  pts[j] = p;
+  ckey[j] = mapk::pack_cell(mapk::cell_of(p.x, inv), mapk::cell_of(p.y, inv), mapk::cell_of(p.z, inv));
+}
+
+__global__ void k_lv_count_cells(const uint64_t* ckey, const int* toff, int na, int n, int* ncell) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  const int a = lv_find(toff, na, j);
+  if (j == toff[a] || ckey[j] != ckey[j - 1]) atomicAdd(&ncell[a], 1);
+}
+
+// k_insert_runs into each candidate's slice, (begin, count) relative to its target
+__global__ void k_lv_insert(const uint64_t* ckey, const LvCand* cd, const int* toff, int na, int n, uint64_t* hkey,
+                            int2* hval) {
+  const int j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n) return;
+  const int a = lv_find(toff, na, j);
+  const LvCand C = cd[a];
+  if (j > C.t_off && ckey[j] == ckey[j - 1]) return;
+  const uint64_t key = ckey[j];
+  const int end = C.t_off + C.nt;
+  int e = j + 1;
+  while (e < end && ckey[e] == key) e++;
+  uint64_t* hk = hkey + C.h_off;
+  uint32_t h = mapk::mix64(key) & C.hmask;
+  while (true) {
+    const unsigned long long prev = atomicCAS((unsigned long long*)&hk[h], (unsigned long long)mapk::kEmptyKey,
+                                              (unsigned long long)key);
+    if (prev == mapk::kEmptyKey) break;
+    h = (h + 1) & C.hmask;
+  }
+  hval[C.h_off + h] = make_int2(j - C.t_off, e - j);
+}
+
+// k_knn<5, 64> with k = 1: a wave per query, searching the target of the query's candidate
+__global__ __launch_bounds__(256) void k_lv_knn(const MapView* views, const IcpDev* st, int skip_done, const float4* q,
+                                                const int* qseg, int nq, float max_d2, float4* out_pts, float* out_d2,
+                                                int* out_found) {
+  const int qi = mapk::xcd_block(blockIdx.x, gridDim.x) * 4 + (int)(threadIdx.x / 64);
+  if (qi >= nq) return;
+  const int a = __builtin_amdgcn_readfirstlane(qseg[qi]);
+  if (skip_done && st[a].done) return;
+  const MapView m = views[a];
+  const float4 p = q[qi];
+  mapk::knn_query<5, 64>(m, make_float4(p.x, p.y, p.z, 0.f), qi, 1, max_d2, out_pts, out_d2, out_found);
+}
+
+__global__ __launch_bounds__(kRed) void k_lv_step(IcpDev* st, const LvCand* cd, const float4* src, const float4* nb,
+                                                  const float* d2, const int* found, IcpParams P) {
+  __shared__ double red[9][kRed];
+  const LvCand C = cd[blockIdx.x];
+  lc_step_body(st + blockIdx.x, src + C.w_off, nb + C.w_off, d2 + C.w_off, found + C.w_off, C.ns, P, red);
+}
+
+__global__ void k_lv_apply(const IcpDev* st, const int* qseg, float4* src, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const IcpDev* s = st + qseg[i];
+  if (!s->run) return;
+  src[i] = lc_tf_f(s->T, src[i]);
+}
+
+__global__ void k_lv_final_tf(const IcpDev* st, const int* qseg, const float4* src, int n, float4* out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  out[i] = lc_tf_f(st[qseg[i]].F, src[i]);
+}
+
+__global__ __launch_bounds__(kRed) void k_lv_fitness(IcpDev* st, const LvCand* cd, const float* d2, const int* found) {
+  __shared__ double red[2][kRed];
+  const LvCand C = cd[blockIdx.x];
+  lc_fitness_body(st + blockIdx.x, d2 + C.w_off, found + C.w_off, C.ns, red);
+}
+
+}  // namespace loopk
+}  // namespace lislam
+
+struct lislam_keyframes {
+  lislam_ctx* ctx = nullptr;
+  int32_t capacity = 0;
+  int64_t point_capacity = 0;
+  float4* pts = nullptr;
+  std::vector<int64_t> off{0};  // keyframe i = pts[off[i], off[i + 1])
+  int32_t size() const { return (int32_t)off.size() - 1; }
+};
+
+struct VerifyState {
+  DBuf T, pieces, pdst, at, tf, flag, pos, seg, sel, selseg, seloff, vx, keys, keys2, idx, idx2, voxoff, tmp;
+  DBuf cand, woff, toff, views, st, src, src0, ftf, qseg, nb, d2, found, tp, owner, owner2, tpts, ckey, ncell, hkey, hval;
+  void* host = nullptr;  // pinned, read back by the host
+  size_t host_bytes = 0;
+  std::vector<double> hT;
+  hipError_t reserve_host(size_t b) {
+    if (b <= host_bytes) return hipSuccess;
+    if (host) (void)hipHostFree(host);
+    host = nullptr;
+    host_bytes = 0;
+    hipError_t e = hipHostMalloc(&host, b * 2);
+    if (e == hipSuccess) host_bytes = b * 2;
+    return e;
+  }
+  ~VerifyState() { if (host) (void)hipHostFree(host); }
+};
+
+static void free_verify_state(VerifyState* v) { delete v; }
+
+namespace {
+
+template <typename T>
+int lv_upload(lislam_ctx* c, DBuf& d, const std::vector<T>& v) {
+  MCHK(c, d.reserve(std::max<size_t>(v.size() * sizeof(T), 16)));
+  // pageable source: the copy has read it when it returns
+  if (!v.empty()) MCHK(c, hipMemcpyAsync(d.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, stream_of(c)));
+  return LISLAM_OK;
+}
+
+int lv_bits(int n) {  // radix passes' bits for values in [0, n)
+  int b = 8;
+  while (b < 32 && (1ll << b) < n) b += 8;
+  return b;
+}
+
+}  // namespace
+
+extern "C" {
+
+int lislam_keyframes_create(lislam_ctx* c, int32_t capacity, int64_t point_capacity, lislam_keyframes** out) {
+  if (!c || !out) return LISLAM_ERR_ARG;
+  *out = nullptr;
+  if (capacity < 1 || point_capacity < 0) return mfail(c, LISLAM_ERR_ARG, "lislam_keyframes_create: invalid capacity");
+  hipSetDevice(c->device);
+  lislam_keyframes* kf = new lislam_keyframes();
+  kf->ctx = c;
+  kf->capacity = capacity;
+  kf->point_capacity = point_capacity;
+  if (hipMalloc((void**)&kf->pts, (size_t)std::max<int64_t>(point_capacity, 1) * sizeof(float4)) != hipSuccess) {
+    (void)hipGetLastError();
+    delete kf;
+    return mfail(c, LISLAM_ERR_DEVICE, "lislam_keyframes_create: allocating %lld points failed", (long long)point_capacity);
+  }
+  kf->off.reserve((size_t)capacity + 1);
+  *out = kf;
+  return LISLAM_OK;
+}
+
+int lislam_keyframes_destroy(lislam_keyframes* kf) {
+  if (!kf) return LISLAM_ERR_ARG;
+  hipSetDevice(kf->ctx->device);
+  (void)hipStreamSynchronize(kf->ctx->stream);
+  if (kf->pts) (void)hipFree(kf->pts);
+  delete kf;
+  return LISLAM_OK;
+}
+
+int lislam_keyframes_size(lislam_keyframes* kf, int32_t* n_keyframes, int64_t* n_points) {
+  if (!kf) return LISLAM_ERR_ARG;
+  if (n_keyframes) *n_keyframes = kf->size();
+  if (n_points) *n_points = kf->off.back();
+  return LISLAM_OK;
+}
+
+int lislam_keyframes_add_clouds(lislam_keyframes* kf, const void* points, const int32_t* counts, int32_t n_clouds) {
+  if (!kf || n_clouds < 0 || (n_clouds > 0 && !counts)) return LISLAM_ERR_ARG;
+  lislam_ctx* c = kf->ctx;
+  int64_t total = 0;
+  for (int k = 0; k < n_clouds; k++) {
+    if (counts[k] < 0) return mfail(c, LISLAM_ERR_ARG, "lislam_keyframes_add_clouds: counts[%d] = %d", k, counts[k]);
+    total += counts[k];
+  }
+  if (total > 0 && !points) return mfail(c, LISLAM_ERR_ARG, "lislam_keyframes_add_clouds: null points");
+  if ((int64_t)kf->size() + n_clouds > kf->capacity)
+    return mfail(c, LISLAM_ERR_CAPACITY, "lislam_keyframes_add_clouds: %d + %d keyframes exceed the capacity %d", kf->size(),
+                 n_clouds, kf->capacity);
+  if (kf->off.back() + total > kf->point_capacity)
+    return mfail(c, LISLAM_ERR_CAPACITY, "lislam_keyframes_add_clouds: %lld + %lld points exceed the capacity %lld",
+                 (long long)kf->off.back(), (long long)total, (long long)kf->point_capacity);
+  if (n_clouds == 0) return LISLAM_OK;
+  hipSetDevice(c->device);
+  if (total > 0) {
+    MCHK(c, hipMemcpyAsync(kf->pts + kf->off.back(), points, (size_t)total * sizeof(float4), hipMemcpyDefault, stream_of(c)));
+    MCHK(c, hipStreamSynchronize(stream_of(c)));  // the caller's array is free on return
+  }
+  for (int k = 0; k < n_clouds; k++) kf->off.push_back(kf->off.back() + counts[k]);
+  return LISLAM_OK;
+}
+
+int lislam_keyframes_add_batch(lislam_keyframes* kf, lislam_batch* b, int32_t first_scan, int32_t n_scans) {
+  if (!kf || !b) return LISLAM_ERR_ARG;
+  lislam_ctx* c = kf->ctx;
+  if (b->ctx != c) return mfail(c, LISLAM_ERR_ARG, "lislam_keyframes_add_batch: the batch belongs to another context");
+  if (first_scan < 0 || n_scans < 0 || (int64_t)first_scan + n_scans > b->max_scans)
+    return mfail(c, LISLAM_ERR_ARG, "lislam_keyframes_add_batch: scans [%d, %d + %d) out of range", first_scan, first_scan,
+                 n_scans);
+  if (!b->fa.track)
+    return mfail(c, LISLAM_ERR_STATE, "lislam_keyframes_add_batch: cloud_track not materialized (want_images=0)");
+  if (first_scan + n_scans > b->extracted)
+    return mfail(c, LISLAM_ERR_STATE, "lislam_keyframes_add_batch: extract %d scans first", first_scan + n_scans);
+  if ((int64_t)kf->size() + n_scans > kf->capacity)
+    return mfail(c, LISLAM_ERR_CAPACITY, "lislam_keyframes_add_batch: %d + %d keyframes exceed the capacity %d", kf->size(),
+                 n_scans, kf->capacity);
+  const int64_t total = (int64_t)n_scans * b->N;
+  if (kf->off.back() + total > kf->point_capacity)
+    return mfail(c, LISLAM_ERR_CAPACITY, "lislam_keyframes_add_batch: %lld + %lld points exceed the capacity %lld",
+                 (long long)kf->off.back(), (long long)total, (long long)kf->point_capacity);
+  if (n_scans == 0) return LISLAM_OK;
+  hipSetDevice(c->device);
+  MCHK(c, hipMemcpyAsync(kf->pts + kf->off.back(), reinterpret_cast<const float4*>(b->fa.track) + (size_t)first_scan * b->N,
+                         (size_t)total * sizeof(float4), hipMemcpyDeviceToDevice, stream_of(c)));
+  for (int k = 0; k < n_scans; k++) kf->off.push_back(kf->off.back() + b->N);
+  return LISLAM_OK;
+}
+
+int lislam_keyframes_download(lislam_keyframes* kf, int32_t index, float* dst, int32_t cap_points, int32_t* n) {
+  if (!kf || cap_points < 0 || (cap_points > 0 && !dst)) return LISLAM_ERR_ARG;
+  lislam_ctx* c = kf->ctx;
+  if (index < 0 || index >= kf->size())
+    return mfail(c, LISLAM_ERR_ARG, "lislam_keyframes_download: index %d out of range (size %d)", index, kf->size());
+  const int64_t cnt = kf->off[index + 1] - kf->off[index];
+  if (n) *n = (int32_t)cnt;
+  if (cap_points < cnt)
+    return mfail(c, LISLAM_ERR_CAPACITY, "lislam_keyframes_download: %lld points, capacity %d", (long long)cnt, cap_points);
+  if (cnt == 0) return LISLAM_OK;
+  hipSetDevice(c->device);
+  MCHK(c, hipMemcpyAsync(dst, kf->pts + kf->off[index], (size_t)cnt * sizeof(float4), hipMemcpyDeviceToHost, stream_of(c)));
+  MCHK(c, hipStreamSynchronize(stream_of(c)));
+  return LISLAM_OK;
+}
+
+int lislam_loop_verify(lislam_keyframes* kf, const lislam_icp_config* cfg, int32_t submap_window, const int32_t* cur_id,
+                       const int32_t* loop_id, int32_t n_loops, const double* T_kf, double* T_icp, double* T_cur2map,
+                       double* fitness, int32_t* info) {
+  if (!kf || !cfg || n_loops < 0 || (n_loops > 0 && (!cur_id || !loop_id || !T_kf))) return LISLAM_ERR_ARG;
+  lislam_ctx* c = kf->ctx;
+  const int nk = kf->size(), w = submap_window, L = n_loops;
+  if (w < 0 || w > 4) return mfail(c, LISLAM_ERR_ARG, "lislam_loop_verify: submap_window %d not in 0..4", w);
+  if (cfg->use_downsample && !(cfg->voxel_size > 0)) return mfail(c, LISLAM_ERR_ARG, "lislam_loop_verify: voxel_size <= 0");
+  for (int k = 0; k < L; k++) {
+    if (cur_id[k] < 0 || cur_id[k] >= nk)
+      return mfail(c, LISLAM_ERR_ARG, "lislam_loop_verify: cur_id[%d] = %d out of range (size %d)", k, cur_id[k], nk);
+    if (loop_id[k] >= nk || loop_id[k] > cur_id[k])
+      return mfail(c, LISLAM_ERR_ARG, "lislam_loop_verify: loop_id[%d] = %d with cur_id %d (size %d)", k, loop_id[k],
+                   cur_id[k], nk);
+  }
+  if (L == 0) return LISLAM_OK;
+  if (L > 0x1fffffff) return mfail(c, LISLAM_ERR_CAPACITY, "lislam_loop_verify: too many candidates");
+  // pieces and segments: 2k = the source of candidate k, 2k + 1 its target
+  const int nseg = 2 * L;
+  std::vector<LvPiece> pc;
+  std::vector<int> pdst, rawoff((size_t)nseg + 1);
+  std::vector<int32_t> inf((size_t)L * 8, 0);
+  int64_t tot = 0;
+  auto piece = [&](int i, int seg) {
+    const int64_t n = kf->off[i + 1] - kf->off[i];
+    if (n > 0 && tot + n <= 0x3fffffff) {
+      pc.push_back(LvPiece{(long long)kf->off[i], (int)tot, (int)n, i, seg});
+      pdst.push_back((int)tot);
+    }
+    tot += n;
+  };
+  for (int k = 0; k < L; k++) {
+    const int cur = cur_id[k], loop = loop_id[k];
+    rawoff[2 * k] = rawoff[2 * k + 1] = (int)std::min<int64_t>(tot, 0x3fffffff);
+    if (loop < 0) {
+      inf[8 * k] = -3;
+      continue;
+    }
+    const int lo = std::max(0, loop - w), hi = std::min(loop + w, cur);
+    if (kf->off[hi + 1] == kf->off[lo]) {  // history_cloud->size() == 0 (:248)
+      inf[8 * k] = -1;
+      continue;
+    }
+    piece(cur, 2 * k);
+    rawoff[2 * k + 1] = (int)std::min<int64_t>(tot, 0x3fffffff);
+    for (int i = lo; i <= hi; i++) piece(i, 2 * k + 1);
+    if (tot > 0x3fffffff) return mfail(c, LISLAM_ERR_CAPACITY, "lislam_loop_verify: the candidates' clouds are too large");
+  }
+  rawoff[nseg] = (int)tot;
+  const int ntot = (int)tot;
+
+  hipSetDevice(c->device);
+  hipStream_t st = stream_of(c);
+  MapScratch& sc = ctx_scratch(c);
+  if (!sc.verify) sc.verify = new VerifyState();
+  VerifyState& V = *sc.verify;
+  V.hT.resize((size_t)nk * 16);
+  MCHK(c, hipMemcpy(V.hT.data(), T_kf, (size_t)nk * 16 * sizeof(double), hipMemcpyDefault));
+  const double* hT = V.hT.data();
+
+  std::vector<int> ns(L, 0), nt(L, 0), act;  // prepared sizes; the candidates that iterate
+  std::vector<LvCand> cd;
+  IcpDev* hst = nullptr;
+  if (ntot > 0) {
+    MRC(lv_upload(c, V.T, V.hT));
+    MRC(lv_upload(c, V.pieces, pc));
+    MRC(lv_upload(c, V.pdst, pdst));
+    MRC(lv_upload(c, V.at, rawoff));
+    MCHK(c, V.tf.reserve((size_t)ntot * sizeof(float4)));
+    MCHK(c, V.sel.reserve((size_t)ntot * sizeof(float4)));
+    MCHK(c, V.flag.reserve((size_t)ntot * 4));
+    MCHK(c, V.pos.reserve((size_t)ntot * 4));
+    MCHK(c, V.seg.reserve((size_t)ntot * 4));
+    MCHK(c, V.selseg.reserve((size_t)ntot * 4));
+    MCHK(c, V.seloff.reserve((size_t)(nseg + 1) * 4));
+    MCHK(c, V.voxoff.reserve((size_t)(nseg + 1) * 4));
+    MCHK(c, V.tmp.reserve(std::max(prims::exclusive_sum_temp_bytes(ntot), prims::sort_temp_bytes(ntot))));
+    MCHK(c, V.reserve_host(std::max<size_t>((size_t)(nseg + 1) * 4, (size_t)L * sizeof(IcpDev))));
+    int* hoff = static_cast<int*>(V.host);
+    // transform + removeNaN + CropBox
+    hipLaunchKernelGGL(k_lv_transform, dim3(blocks(ntot)), dim3(256), 0, st, kf->pts, V.pieces.as<LvPiece>(),
+                       V.pdst.as<int>(), (int)pc.size(), V.T.as<double>(), ntot, cfg->use_crop ? 1 : 0, -cfg->crop_size,
+                       cfg->crop_size, V.tf.as<float4>(), V.flag.as<int>(), V.seg.as<int>());
+    MCHK(c, prims::exclusive_sum(V.tmp.p, V.flag.as<int>(), V.pos.as<int>(), ntot, st));
+    hipLaunchKernelGGL(k_lv_compact, dim3(blocks(ntot)), dim3(256), 0, st, V.tf.as<float4>(), V.flag.as<int>(),
+                       V.pos.as<int>(), V.seg.as<int>(), ntot, V.sel.as<float4>(), V.selseg.as<int>());
+    hipLaunchKernelGGL(k_lv_offsets, dim3(blocks(nseg + 1)), dim3(256), 0, st, V.pos.as<int>(), V.flag.as<int>(),
+                       V.at.as<int>(), nseg + 1, ntot, V.seloff.as<int>());
+    MCHK(c, hipGetLastError());
+    MCHK(c, hipMemcpyAsync(hoff, V.seloff.p, (size_t)(nseg + 1) * 4, hipMemcpyDeviceToHost, st));
+    MCHK(c, hipStreamSynchronize(st));
+    const int nsel = hoff[nseg];
+    const float4* prepared = V.sel.as<float4>();  // the segments after filtering, back to back
+    if (cfg->use_downsample && nsel > 0) {
+      // VoxelGrid of every segment: out = V.tf (its points are all in V.sel by now)
+      MCHK(c, V.vx.reserve((size_t)nseg * sizeof(LvVox)));
+      MCHK(c, V.keys.reserve((size_t)nsel * 8));
+      MCHK(c, V.keys2.reserve((size_t)nsel * 8));
+      MCHK(c, V.idx.reserve((size_t)nsel * 4));
+      MCHK(c, V.idx2.reserve((size_t)nsel * 4));
+      const float inv = 1.0f / cfg->voxel_size;
+      hipLaunchKernelGGL(k_lv_bounds, dim3(nseg), dim3(1024), 0, st, prepared, V.seloff.as<int>(), inv, V.vx.as<LvVox>());
+      hipLaunchKernelGGL(k_lv_keys, dim3(blocks(nsel)), dim3(256), 0, st, prepared, V.selseg.as<int>(), V.seloff.as<int>(),
+                         V.vx.as<LvVox>(), inv, nsel, V.keys.as<uint64_t>(), V.idx.as<int>());
+      MCHK(c, prims::sort_pairs<uint64_t>(V.tmp.p, V.keys.as<uint64_t>(), V.keys2.as<uint64_t>(), V.idx.as<int>(),
+                                          V.idx2.as<int>(), nsel, 32 + lv_bits(nseg), st));
+      hipLaunchKernelGGL(k_lv_runs, dim3(blocks(nsel)), dim3(256), 0, st, V.keys2.as<uint64_t>(), nsel, V.flag.as<int>());
+      MCHK(c, prims::exclusive_sum(V.tmp.p, V.flag.as<int>(), V.pos.as<int>(), nsel, st));
+      hipLaunchKernelGGL(k_lv_centroids, dim3(blocks(nsel)), dim3(256), 0, st, prepared, V.keys2.as<uint64_t>(),
+                         V.idx2.as<int>(), V.pos.as<int>(), V.flag.as<int>(), nsel, V.tf.as<float4>());
+      hipLaunchKernelGGL(k_lv_offsets, dim3(blocks(nseg + 1)), dim3(256), 0, st, V.pos.as<int>(), V.flag.as<int>(),
+                         V.seloff.as<int>(), nseg + 1, nsel, V.voxoff.as<int>());
+      MCHK(c, hipGetLastError());
+      MCHK(c, hipMemcpyAsync(hoff, V.voxoff.p, (size_t)(nseg + 1) * 4, hipMemcpyDeviceToHost, st));
+      MCHK(c, hipStreamSynchronize(st));
+      prepared = V.tf.as<float4>();
+    }
+    // the sizes decide who iterates
+    int64_t wtot = 0, ttot = 0;
+    for (int k = 0; k < L; k++) {
+      if (inf[8 * k] < 0) continue;
+      ns[k] = hoff[2 * k + 1] - hoff[2 * k];
+      nt[k] = hoff[2 * k + 2] - hoff[2 * k + 1];
+      inf[8 * k + 4] = ns[k];
+      inf[8 * k + 5] = nt[k];
+      if (ns[k] <= 10 || nt[k] <= 10) {
+        inf[8 * k] = -2;
+        continue;
+      }
+      LvCand C;
+      C.w_off = (int)wtot; C.ns = ns[k];
+      C.t_off = (int)ttot; C.nt = nt[k];
+      C.src_vox = hoff[2 * k]; C.tgt_vox = hoff[2 * k + 1];
+      C.h_off = 0; C.hmask = 0;
+      cd.push_back(C);
+      act.push_back(k);
+      wtot += ns[k];
+      ttot += nt[k];
+    }
+    const int na = (int)act.size(), nw = (int)wtot, ntg = (int)ttot;
+    if (na > 0) {
+      std::vector<int> woff(na), toff(na);
+      for (int a = 0; a < na; a++) { woff[a] = cd[a].w_off; toff[a] = cd[a].t_off; }
+      MRC(lv_upload(c, V.woff, woff));
+      MRC(lv_upload(c, V.toff, toff));
+      MRC(lv_upload(c, V.cand, cd));
+      MCHK(c, V.src.reserve((size_t)nw * sizeof(float4)));
+      MCHK(c, V.src0.reserve((size_t)nw * sizeof(float4)));
+      MCHK(c, V.ftf.reserve((size_t)nw * sizeof(float4)));
+      MCHK(c, V.nb.reserve((size_t)nw * sizeof(float4)));
+      MCHK(c, V.qseg.reserve((size_t)nw * 4));
+      MCHK(c, V.d2.reserve((size_t)nw * 4));
+      MCHK(c, V.found.reserve((size_t)nw * 4));
+      MCHK(c, V.tp.reserve((size_t)ntg * sizeof(float4)));
+      MCHK(c, V.tpts.reserve((size_t)ntg * sizeof(float4)));
+      MCHK(c, V.keys.reserve((size_t)ntg * 8));
+      MCHK(c, V.keys2.reserve((size_t)ntg * 8));
+      MCHK(c, V.ckey.reserve((size_t)ntg * 8));
+      MCHK(c, V.idx.reserve((size_t)ntg * 4));
+      MCHK(c, V.idx2.reserve((size_t)ntg * 4));
+      MCHK(c, V.owner.reserve((size_t)ntg * 4));
+      MCHK(c, V.owner2.reserve((size_t)ntg * 4));
+      MCHK(c, V.ncell.reserve((size_t)na * 4));
+      MCHK(c, V.tmp.reserve(prims::sort_temp_bytes(ntg)));
+      const float cell = std::max(1.0f, cfg->use_downsample ? 2.0f * cfg->voxel_size : 1.0f);
+      const float inv_cell = 1.0f / cell;
+      hipLaunchKernelGGL(k_lv_src, dim3(blocks(nw)), dim3(256), 0, st, prepared, V.cand.as<LvCand>(), V.woff.as<int>(), na, nw,
+                         V.src.as<float4>(), V.src0.as<float4>(), V.qseg.as<int>());
+      int* hcell = static_cast<int*>(V.host);
+      {
+        // the targets' cell index: sorted by cell, then (stable) by candidate
+        TimedScope ts(c, kT_rebuild);
+        hipLaunchKernelGGL(k_lv_tgt, dim3(blocks(ntg)), dim3(256), 0, st, prepared, V.cand.as<LvCand>(), V.toff.as<int>(), na,
+                           ntg, inv_cell, V.tp.as<float4>(), V.keys.as<uint64_t>(), V.idx.as<int>());
+        MCHK(c, prims::sort_pairs<uint64_t>(V.tmp.p, V.keys.as<uint64_t>(), V.keys2.as<uint64_t>(), V.idx.as<int>(),
+                                            V.idx2.as<int>(), ntg, 64, st));
+        const int* perm = V.idx2.as<int>();
+        if (na > 1) {
+          hipLaunchKernelGGL(k_lv_owner, dim3(blocks(ntg)), dim3(256), 0, st, V.idx2.as<int>(), V.toff.as<int>(), na, ntg,
+                             V.owner.as<uint32_t>());
+          MCHK(c, prims::sort_pairs<uint32_t>(V.tmp.p, V.owner.as<uint32_t>(), V.owner2.as<uint32_t>(), V.idx2.as<int>(),
+                                              V.idx.as<int>(), ntg, lv_bits(na), st));
+          perm = V.idx.as<int>();
+        }
+        hipLaunchKernelGGL(k_lv_tgather, dim3(blocks(ntg)), dim3(256), 0, st, V.tp.as<float4>(), perm, ntg, inv_cell,
+                           V.tpts.as<float4>(), V.ckey.as<uint64_t>());
+        MCHK(c, hipMemsetAsync(V.ncell.p, 0, (size_t)na * 4, st));
+        hipLaunchKernelGGL(k_lv_count_cells, dim3(blocks(ntg)), dim3(256), 0, st, V.ckey.as<uint64_t>(), V.toff.as<int>(), na,
+                           ntg, V.ncell.as<int>());
+        MCHK(c, hipGetLastError());
+        MCHK(c, hipMemcpyAsync(hcell, V.ncell.p, (size_t)na * 4, hipMemcpyDeviceToHost, st));
+        MCHK(c, hipStreamSynchronize(st));
+        int64_t htot = 0;
+        for (int a = 0; a < na; a++) {
+          const uint32_t cap = pow2_at_least((uint64_t)hcell[a] * 2);
+          cd[a].h_off = (int)htot;
+          cd[a].hmask = cap - 1;
+          htot += cap;
+          if (htot > 0x7fffffff) return mfail(c, LISLAM_ERR_CAPACITY, "lislam_loop_verify: the cell tables are too large");
+        }
+        MRC(lv_upload(c, V.cand, cd));
+        MCHK(c, V.hkey.reserve((size_t)htot * 8));
+        MCHK(c, V.hval.reserve((size_t)htot * 8));
+        MCHK(c, hipMemsetAsync(V.hkey.p, 0xff, (size_t)htot * 8, st));
+        hipLaunchKernelGGL(k_lv_insert, dim3(blocks(ntg)), dim3(256), 0, st, V.ckey.as<uint64_t>(), V.cand.as<LvCand>(),
+                           V.toff.as<int>(), na, ntg, V.hkey.as<uint64_t>(), V.hval.as<int2>());
+      }
+      std::vector<MapView> views(na);
+      for (int a = 0; a < na; a++) {
+        MapView& v = views[a];
+        v.pts = V.tpts.as<float4>() + cd[a].t_off;
+        v.hkey = V.hkey.as<uint64_t>() + cd[a].h_off;
+        v.hval = V.hval.as<int2>() + cd[a].h_off;
+        v.hmask = cd[a].hmask;
+        v.cell = cell;
+        v.inv_cell = inv_cell;
+        v.n = cd[a].nt;
+        v.scan_shell = mapk::scan_shell_for(cd[a].nt);
+        v.near2 = mapk::knn_near2(cell);
+      }
+      MRC(lv_upload(c, V.views, views));
+      // ICP states
+      hst = static_cast<IcpDev*>(V.host);
+      std::memset(hst, 0, (size_t)na * sizeof(IcpDev));
+      for (int a = 0; a < na; a++) {
+        for (int k = 0; k < 16; k++) hst[a].T[k] = hst[a].F[k] = (k % 5 == 0) ? 1.f : 0.f;
+        hst[a].prev_mse = DBL_MAX;
+        hst[a].nq = cd[a].ns;
+      }
+      MCHK(c, V.st.reserve((size_t)na * sizeof(IcpDev)));
+      IcpDev* d = V.st.as<IcpDev>();
+      MCHK(c, hipMemcpyAsync(d, hst, (size_t)na * sizeof(IcpDev), hipMemcpyHostToDevice, st));
+      IcpParams P;
+      P.max_iter = cfg->max_iterations;
+      P.rot_thr = 1.0 - cfg->transformation_epsilon;
+      P.trans_thr = cfg->transformation_epsilon;
+      P.mse_abs = 1e-12;
+      P.mse_rel = cfg->euclidean_fitness_epsilon;
+      const float md2 = cfg->max_correspondence_distance * cfg->max_correspondence_distance;
+      const int cap = std::max(cfg->max_iterations, 1);
+      const int knn_blocks = blocks((int64_t)nw * 64);
+      constexpr int kChunk = 6;
+      bool all_done = false;
+      for (int it0 = 0; it0 < cap && !all_done; it0 += kChunk) {
+        for (int j = 0; j < kChunk && it0 + j < cap; j++) {
+          {
+            TimedScope ts(c, kT_knn);
+            hipLaunchKernelGGL(k_lv_knn, dim3(knn_blocks), dim3(256), 0, st, V.views.as<MapView>(), d, 1, V.src.as<float4>(),
+                               V.qseg.as<int>(), nw, md2, V.nb.as<float4>(), V.d2.as<float>(), V.found.as<int>());
+          }
+          {
+            TimedScope ts(c, kT_icp_step);
+            hipLaunchKernelGGL(k_lv_step, dim3(na), dim3(kRed), 0, st, d, V.cand.as<LvCand>(), V.src.as<float4>(),
+                               V.nb.as<float4>(), V.d2.as<float>(), V.found.as<int>(), P);
+          }
+          TimedScope ts(c, kT_icp_apply);
+          hipLaunchKernelGGL(k_lv_apply, dim3(blocks(nw)), dim3(256), 0, st, d, V.qseg.as<int>(), V.src.as<float4>(), nw);
+        }
+        MCHK(c, hipGetLastError());
+        MCHK(c, hipMemcpyAsync(hst, d, (size_t)na * sizeof(IcpDev), hipMemcpyDeviceToHost, st));
+        MCHK(c, hipStreamSynchronize(st));
+        all_done = true;
+        for (int a = 0; a < na; a++) all_done = all_done && hst[a].done;
+      }
+      if (!all_done) return mfail(c, LISLAM_ERR_STATE, "lislam_loop_verify: iteration loop did not terminate");
+      // fitness
+      hipLaunchKernelGGL(k_lv_final_tf, dim3(blocks(nw)), dim3(256), 0, st, d, V.qseg.as<int>(), V.src0.as<float4>(), nw,
+                         V.ftf.as<float4>());
+      {
+        TimedScope ts(c, kT_knn);
+        hipLaunchKernelGGL(k_lv_knn, dim3(knn_blocks), dim3(256), 0, st, V.views.as<MapView>(), d, 0, V.ftf.as<float4>(),
+                           V.qseg.as<int>(), nw, mapk::kInf, V.nb.as<float4>(), V.d2.as<float>(), V.found.as<int>());
+      }
+      hipLaunchKernelGGL(k_lv_fitness, dim3(na), dim3(kRed), 0, st, d, V.cand.as<LvCand>(), V.d2.as<float>(),
+                         V.found.as<int>());
+      MCHK(c, hipGetLastError());
+      MCHK(c, hipMemcpyAsync(hst, d, (size_t)na * sizeof(IcpDev), hipMemcpyDeviceToHost, st));
+      MCHK(c, hipStreamSynchronize(st));
+    }
+  }
+  // results
+  std::vector<int> slot(L, -1);
+  for (size_t a = 0; a < act.size(); a++) slot[act[a]] = (int)a;
+  for (int k = 0; k < L; k++) {
+    const double* Tcur = hT + 16 * (size_t)cur_id[k];
+    double Ti[16], Tc[16], fit = DBL_MAX;
+    for (int e = 0; e < 16; e++) { Ti[e] = (e % 5 == 0) ? 1.0 : 0.0; Tc[e] = Tcur[e]; }
+    int32_t* I = &inf[8 * (size_t)k];
+    if (slot[k] >= 0) {
+      const IcpDev& h = hst[slot[k]];
+      fit = h.fitness;
+      I[1] = (h.state >= 1 && h.state <= 4) ? 1 : 0;
+      I[2] = h.state;
+      I[3] = h.iter;
+      I[6] = h.ncorr;
+      I[0] = (I[1] && fit <= cfg->fitness_threshold) ? 1 : 0;
+      for (int e = 0; e < 16; e++) Ti[e] = h.F[e];
+      for (int r = 0; r < 4; r++)
+        for (int col = 0; col < 4; col++)
+          Tc[4 * r + col] = ((Ti[4 * r] * Tcur[col] + Ti[4 * r + 1] * Tcur[4 + col]) + Ti[4 * r + 2] * Tcur[8 + col]) +
+                            Ti[4 * r + 3] * Tcur[12 + col];
+    }
+    if (T_icp) std::memcpy(T_icp + 16 * (size_t)k, Ti, sizeof(Ti));
+    if (T_cur2map) std::memcpy(T_cur2map + 16 * (size_t)k, Tc, sizeof(Tc));
+    if (fitness) fitness[k] = fit;
+    if (info) std::memcpy(info + 8 * (size_t)k, I, 8 * sizeof(int32_t));
+  }
+  return LISLAM_OK;
 }
 
 }  // extern "C"

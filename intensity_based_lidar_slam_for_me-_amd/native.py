@@ -45,6 +45,8 @@ EXPORTED_SYMBOLS = (
     "lislam_intensity_tracker_step", "lislam_batch_intensity_odometry", "lislam_batch_orb_cascade_info", "lislam_batch_ground", "lislam_ground_extract",
     "lislam_lmap_create", "lislam_lmap_destroy", "lislam_lmap_step", "lislam_lmap_counts", "lislam_lmap_points",
     "lislam_batch_odometry_gated", "lislam_odom_step_gated", "lislam_batch_mapopt", "lislam_batch_mapopt_corner", "lislam_loop_icp", "lislam_odom_fuser_create", "lislam_odom_fuser_destroy", "lislam_odom_fuse",
+    "lislam_keyframes_create", "lislam_keyframes_destroy", "lislam_keyframes_size", "lislam_keyframes_add_clouds",
+    "lislam_keyframes_add_batch", "lislam_keyframes_download", "lislam_loop_verify",
     "lislam_place_create", "lislam_place_destroy", "lislam_place_size", "lislam_place_add_clouds", "lislam_place_add_batch",
     "lislam_place_detect", "lislam_place_distance", "lislam_place_download",
     "lislam_bow_create", "lislam_bow_destroy", "lislam_bow_size", "lislam_bow_add", "lislam_bow_add_batch",
@@ -273,6 +275,13 @@ def load(path: str = LIB_PATH):
     L.lislam_batch_mapopt.argtypes = [vp, vp, _i32, vp, vp, vp, vp]
     L.lislam_batch_mapopt_corner.argtypes = [vp, vp, vp, _i32, vp, vp, vp, vp]
     L.lislam_loop_icp.argtypes = [vp, ctypes.POINTER(IcpConfig), vp, _i32, vp, vp, vp, _i32, vp, vp, vp, vp, vp]
+    L.lislam_keyframes_create.argtypes = [vp, _i32, ctypes.c_int64, ctypes.POINTER(vp)]
+    L.lislam_keyframes_destroy.argtypes = [vp]
+    L.lislam_keyframes_size.argtypes = [vp, _i32p, ctypes.POINTER(ctypes.c_int64)]
+    L.lislam_keyframes_add_clouds.argtypes = [vp, vp, vp, _i32]
+    L.lislam_keyframes_add_batch.argtypes = [vp, vp, _i32, _i32]
+    L.lislam_keyframes_download.argtypes = [vp, _i32, vp, _i32, _i32p]
+    L.lislam_loop_verify.argtypes = [vp, ctypes.POINTER(IcpConfig), _i32, vp, vp, _i32, vp, vp, vp, vp, vp]
     L.lislam_odom_fuser_create.argtypes = [vp, ctypes.POINTER(vp)]
     L.lislam_odom_fuser_destroy.argtypes = [vp]
     L.lislam_odom_fuse.argtypes = [vp, vp, vp, vp, _i32, vp]
