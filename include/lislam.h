@@ -480,6 +480,64 @@ int lislam_batch_mapopt(lislam_batch* b, lislam_map* m, int32_t scan, const doub
  * pc_corner topic, mapOptimizationNode.cpp:63). corner_map NULL = lislam_batch_mapopt. */
 int lislam_batch_mapopt_corner(lislam_batch* b, lislam_map* m, lislam_map* corner_map, int32_t scan,
                                const double* odom, double* state, double* out_pose, int32_t* summary);
+/* ---- mapOptimization's ORB keyframe sliding window (keyframe_sliding_window_,
+ * mapOptimization.cpp:155-169, :295-361, :481-493; SLIDING_WINDOW_SIZE = config sliding_window_size).
+ * A keyframe is its ORB descriptors desc[n][32], their sensor-frame points p3d[n][4] (x, y, z, -)
+ * and a pose (q x,y,z,w, t).  Device resident; pointers may be host or device memory. */
+typedef struct lislam_mapwin lislam_mapwin;
+/* window_size 0..16 (0: the window is always empty when it is read, :491-493), feature_capacity
+ * 1..4096 per keyframe; anything else LISLAM_ERR_ARG.  A call with more than feature_capacity
+ * features returns LISLAM_ERR_CAPACITY and changes nothing. */
+int lislam_mapwin_create(lislam_ctx* ctx, int32_t window_size, int32_t feature_capacity, lislam_mapwin** out);
+int lislam_mapwin_destroy(lislam_mapwin* win);
+int lislam_mapwin_size(lislam_mapwin* win, int32_t* n);
+/* emplace_back, then pop_front while the size exceeds window_size (:488-493). */
+int lislam_mapwin_push(lislam_mapwin* win, const uint8_t* desc, const float* p3d, int32_t n, const double* pose);
+/* Keyframe `index` (0 = oldest): up to cap features into desc / p3d (nullable), *n, pose[7] (nullable). */
+int lislam_mapwin_keyframe(lislam_mapwin* win, int32_t index, uint8_t* desc, float* p3d, int32_t cap, int32_t* n,
+                           double* pose);
+/* cv::BFMatcher().match(desc, keyframe descriptors) (:305-307: NORM_L2, no cross-check) against
+ * every window keyframe, newest first: matches[window][n][2] = train index (the first of equal
+ * distances) and the integer sum of squared byte differences (the DMatch distance is its sqrtf);
+ * both -1 when the keyframe has no descriptors. */
+int lislam_mapwin_match(lislam_mapwin* win, const uint8_t* desc, int32_t n, int32_t* matches);
+/* The window loop (:295-361) for a current keyframe (desc, p3d, n) at `pose`, against the whole
+ * window in one set of launches.  Per window keyframe, newest first: the matches (M = n, or 0 when
+ * either side is empty), used only if M > 100 (:309); std::sort by distance, equal distances in
+ * query order (:312); G = #{i >= 0 : i < (double)M * 0.2} (:314); used only if G > 50, G != M and
+ * the two descriptor counts differ (:327); of the first G matches those whose map-frame points
+ * (each keyframe's own pose, :339-340) lie within 0.3 m (:342-346) give a
+ * FeatureMatchingResidual(current point (sensor frame), window point (map frame)) (:348-354).
+ * rec[cap][9] = kind-3 records (src, dst, 0, 0, 0), window keyframes newest to oldest, matches in
+ * sorted order; *n_rec their number (more than cap: LISLAM_ERR_CAPACITY).  info[window_size][6]
+ * (nullable), a row per window keyframe, newest first: train descriptors, M, G, used (0 / 1),
+ * blocks kept, offset of its first block.  pairs[cap][3] (nullable) = window row, query index,
+ * train index of each block. */
+int lislam_mapwin_records(lislam_mapwin* win, const uint8_t* desc, const float* p3d, int32_t n, const double* pose,
+                          double* rec, int32_t cap, int32_t* n_rec, int32_t* info, int32_t* pairs);
+/* lislam_mapopt_step_corner with the window: the FeatureMatchingResiduals of (desc, p3d, nf) at the
+ * initial guess (:112, :168-169) join the ground planes' problem, feature blocks first; after the
+ * solve the keyframe enters the window with the optimised pose on CONVERGENCE, else with the
+ * initial guess (:481-493).  The first call (empty map, Build) pushes nothing (:173-196, :218).
+ * summary[5] = planes, iterations, termination (-1: built), feature blocks, window keyframes used.
+ * win NULL or of window_size 0: lislam_mapopt_step_corner's outputs, bit for bit. */
+int lislam_mapopt_step_window(lislam_map* m, lislam_map* corner_map, lislam_mapwin* win, const float* ground, int32_t n,
+                              const float* corner, int32_t nc, const uint8_t* desc, const float* p3d, int32_t nf,
+                              const double* odom, double* state, double* out_pose, int32_t* summary);
+/* lislam_orb_detect with mapOptimization's extractPointsAndFilterZeroValue (mapOptimization.cpp:
+ * 604-632): a keypoint is dropped only when |x|, |y| and |z| of its point are all below 0.01
+ * (the feature tracker's drops on |x| alone). */
+int lislam_orb_detect_map(lislam_ctx* ctx, const uint8_t* image, const float* cloud_track, const uint8_t* mask,
+                          int32_t H, int32_t W, int32_t nfeatures, float* kp, uint8_t* desc, float* p3d, int32_t cap,
+                          int32_t* n);
+/* lislam_batch_mapopt_corner with the window: cv::ORB::create(nfeatures, ...) features of the
+ * scan's a1 intensity image and cloud_track (want_images = 1) as lislam_orb_detect_map finds them
+ * (mask H x W, nullable) never leave the device.  Pass NUM_ORB_FEATURES * 2 as nfeatures (:155).
+ * summary[5] as lislam_mapopt_step_window. */
+int lislam_batch_mapopt_window(lislam_batch* b, lislam_map* m, lislam_map* corner_map, lislam_mapwin* win, int32_t scan,
+                               int32_t nfeatures, const uint8_t* mask, const double* odom, double* state,
+                               double* out_pose, int32_t* summary);
+
 /* laserMapping::process optimization (laserMapping.cpp:620-850) against a corner map and a surf
  * map: the downsampled current corner / surf clouds (stride 4), pose x (in/out), two outer
  * passes of association + Ceres(4 it).  stats[4] = corner / surf blocks of each pass. */
@@ -817,7 +875,7 @@ int lislam_pgo_poses(lislam_pgo* p, int32_t first, int32_t n, double* pose7, flo
  * while recording).  lislam_map_kernel_times synchronizes, returns the total ms and launch count
  * per kernel since the previous read (arrays of LISLAM_MAP_NUM_KERNELS, in the order below) and
  * clears the record. */
-#define LISLAM_MAP_NUM_KERNELS 22 /* k_knn, k_fit, k_lm_eval, k_lm_step, map rebuild (keys + sort +
+#define LISLAM_MAP_NUM_KERNELS 25 /* k_knn, k_fit, k_lm_eval, k_lm_step, map rebuild (keys + sort +
                                      gather + cell table), Add_Points downsample (claim + resolve),
                                      k_orb_pyramid, k_orb_fast, k_orb_select, k_orb_finish,
                                      k_orb_blur (the padded-level blur of images too large for
@@ -826,7 +884,8 @@ int lislam_pgo_poses(lislam_pgo* p, int32_t first, int32_t n, double* pose7, flo
                                      k_lc_step, k_lc_apply, k_fuse, k_orb_roiblur (the ROI blur +
                                      border rows after k_orb_pyramid), k_lm_solve (a whole pose
                                      solve in one launch; k_lm_eval / k_lm_step are no longer
-                                     launched) */
+                                     launched), k_mw_match, k_mw_select, k_mw_gate (the sliding
+                                     window's L2 match, selection and gate) */
 int lislam_map_set_timing(lislam_ctx* ctx, int32_t enable);
 int lislam_map_kernel_times(lislam_ctx* ctx, float* ms, int32_t* launches);
 

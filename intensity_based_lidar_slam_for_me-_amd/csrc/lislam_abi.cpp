@@ -15,6 +15,7 @@
 #include "lislam_batch.hpp"
 #include "lislam_ctx.hpp"
 #include "lislam_internal.hpp"
+#include "lislam_mapwin.hpp"
 
 using namespace lislam;
 
@@ -501,6 +502,53 @@ int lislam_batch_mapopt_corner(lislam_batch* b, lislam_map* m, lislam_map* cm, i
   return lislam_mapopt_step_corner(m, cm, reinterpret_cast<const float*>(dst), ng + nlf,
                                    reinterpret_cast<const float*>(dst + (size_t)(ng + nlf) * 16), nls, odom, state,
                                    out_pose, summary);
+}
+
+// With the ORB keyframe sliding window: the scan's features (mapOptimization.cpp:155-165) are
+// detected from its a1 intensity image and cloud_track into the window's free slot on the device;
+// only their count comes back.
+int lislam_batch_mapopt_window(lislam_batch* b, lislam_map* m, lislam_map* cm, lislam_mapwin* win, int32_t scan,
+                               int32_t nfeatures, const uint8_t* mask, const double* odom, double* state,
+                               double* out_pose, int32_t* summary) {
+  if (!win || lislam::mapwin::window_size(win) == 0) {
+    const int rc = lislam_batch_mapopt_corner(b, m, cm, scan, odom, state, out_pose, summary);
+    if (rc == LISLAM_OK && summary) summary[3] = summary[4] = 0;
+    return rc;
+  }
+  if (!b || !m || !odom || !state || scan < 0 || scan >= b->max_scans || lislam::mapwin::context(win) != b->ctx)
+    return LISLAM_ERR_ARG;
+  SETTLE(b);
+  lislam_ctx* c = b->ctx;
+  hipSetDevice(c->device);
+  const void *img = nullptr, *trk = nullptr;
+  int ni = 0, ntk = 0;
+  size_t ei = 0, et = 0;
+  int rc = output_source(b, LISLAM_OUT_IMAGE_INTENSITY, scan, &img, &ni, &ei);
+  if (rc) return rc;
+  if ((rc = output_source(b, LISLAM_OUT_CLOUD_TRACK, scan, &trk, &ntk, &et))) return rc;
+  int nf = 0;
+  uint8_t* ddesc = lislam::mapwin::stage_desc(win);
+  float* dp3d = lislam::mapwin::stage_p3d(win);
+  if ((rc = lislam_orb_detect_map(c, static_cast<const uint8_t*>(img), static_cast<const float*>(trk), mask, c->cfg.n_scans,
+                                  c->cfg.width, nfeatures, nullptr, ddesc, dp3d, lislam::mapwin::feature_capacity(win), &nf)))
+    return rc;
+  const void *g = nullptr, *lf = nullptr, *ls = nullptr;
+  int ng = 0, nlf = 0, nls = 0;
+  size_t eg = 0, elf = 0, els = 0;
+  if ((rc = output_source(b, LISLAM_OUT_GROUND, scan, &g, &ng, &eg))) return rc;
+  if ((rc = output_source(b, LISLAM_OUT_LESS_FLAT, scan, &lf, &nlf, &elf))) return rc;
+  if (cm && (rc = output_source(b, LISLAM_OUT_LESS_SHARP, scan, &ls, &nls, &els))) return rc;
+  const size_t bytes = (size_t)(ng + nlf + nls) * 16;
+  if ((rc = rc_wire(b, std::max<size_t>(bytes, 16)))) return fail(c, rc, "lislam_batch_mapopt_window: staging allocation");
+  uint8_t* dst = static_cast<uint8_t*>(b->wire);
+  if (ng) HIPCHK(c, hipMemcpyAsync(dst, g, (size_t)ng * 16, hipMemcpyDeviceToDevice, c->stream));
+  if (nlf) HIPCHK(c, hipMemcpyAsync(dst + (size_t)ng * 16, lf, (size_t)nlf * 16, hipMemcpyDeviceToDevice, c->stream));
+  if (nls)
+    HIPCHK(c, hipMemcpyAsync(dst + (size_t)(ng + nlf) * 16, ls, (size_t)nls * 16, hipMemcpyDeviceToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return lislam_mapopt_step_window(m, cm, win, reinterpret_cast<const float*>(dst), ng + nlf,
+                                   reinterpret_cast<const float*>(dst + (size_t)(ng + nlf) * 16), nls, ddesc, dp3d, nf,
+                                   odom, state, out_pose, summary);
 }
 
 int lislam_batch_download_cloud(lislam_batch* b, int32_t what, int32_t scan, void* dst, const lislam_point_layout* layout,

@@ -38,6 +38,7 @@
 #include "lislam_device.hpp"
 #include "lislam_lm.hpp"
 #include "lislam_lm_wave.hpp"
+#include "lislam_mapwin.hpp"
 
 namespace lislam {
 namespace mapk {
@@ -1844,8 +1845,12 @@ static int corner_map_update(lislam_map* cm, const float* corner, int nc, const 
   return LISLAM_OK;
 }
 
-int lislam_mapopt_step_corner(lislam_map* m, lislam_map* cm, const float* ground, int32_t n, const float* corner,
-                              int32_t nc, const double* odom, double* state, double* out_pose, int32_t* summary) {
+// The step with (win) or without (null) the ORB keyframe sliding window; summary = planes,
+// iterations, termination, and with nsum == 5 feature blocks, window keyframes used.  Without a
+// window the launches are lislam_mapopt_step_corner's, one for one.
+static int mapopt_step_impl(lislam_map* m, lislam_map* cm, lislam_mapwin* win, const float* ground, int32_t n,
+                            const float* corner, int32_t nc, const uint8_t* desc, const float* p3d, int32_t nf,
+                            const double* odom, double* state, double* out_pose, int32_t* summary, int nsum) {
   if (!m || n < 0 || (n > 0 && !ground) || !odom || !state || nc < 0 || (nc > 0 && !corner) ||
       (cm && (cm->ctx != m->ctx || cm == m)))
     return LISLAM_ERR_ARG;
@@ -1853,13 +1858,16 @@ int lislam_mapopt_step_corner(lislam_map* m, lislam_map* cm, const float* ground
   hipSetDevice(c->device);
   MapScratch& sc = m->sc;
   hipStream_t st = stream_of(c);
+  if (win) MRC(mapwin::stage(win, desc, p3d, nf));  // before anything changes: too many features change nothing
+  int hwin[mapwin::kMaxWindow * 6 + 2] = {};
+  int nwin = 0;
   // device pose block: [0,7) state, [8,15) odom, [16,23) x, [24,31) keyframe pose
   MCHK(c, sc.x.reserve(40 * 8));
   double* dp = sc.x.as<double>();
   MCHK(c, hipMemcpyAsync(dp, state, 56, hipMemcpyDefault, st));
   MCHK(c, hipMemcpyAsync(dp + 8, odom, 56, hipMemcpyDefault, st));
   hipLaunchKernelGGL(k_mapopt_pose, dim3(1), dim3(64), 0, st, 0, dp, dp + 8, dp + 16, (const LmDev*)nullptr, dp + 24);
-  int32_t summ[3] = {0, 0, -1};
+  int32_t summ[5] = {0, 0, -1, 0, 0};
   MRC(stage_points(c, sc, sc.vout, ground, n, 4));  // sensor-frame ground cloud (float4)
   if (m->n == 0) {  // first keyframe: Build with the transformed raw cloud (mapOptimization.cpp:185-192)
     MCHK(c, m->tmp.reserve((size_t)std::max(n, 1) * 16));
@@ -1885,11 +1893,27 @@ int lislam_mapopt_step_corner(lislam_map* m, lislam_map* cm, const float* ground
     MCHK(c, sc.rec.reserve((size_t)std::max(n, 1) * 72));
     MCHK(c, sc.kind.reserve((size_t)std::max(n, 1) * 4));
     MRC(associate_device(m, 1, voxbuf.as<float>(), 4, nvox, n, dp + 16, sc.rec.as<double>(), sc.kind.as<int>()));
-    MRC(solve_device(c, sc, sc.rec.as<double>(), sc.kind.as<int>(), nvox, n, dp + 16, 10, nullptr, nullptr));
+    if (win) {
+      // mapOptimization.cpp:295-361 at the initial guess, then the planes behind the feature
+      // blocks: one problem, one loss (:233, :354, :424)
+      MRC(mapwin::records(win, dp + 16, n));
+      MRC(mapwin::append(win, sc.rec.as<double>(), sc.kind.as<int>(), nvox, n));
+      MRC(solve_device(c, sc, mapwin::rec(win), mapwin::kind(win), mapwin::total(win), mapwin::capacity_records(win) + n,
+                       dp + 16, 10, nullptr, nullptr));
+    } else {
+      MRC(solve_device(c, sc, sc.rec.as<double>(), sc.kind.as<int>(), nvox, n, dp + 16, 10, nullptr, nullptr));
+    }
     LmDev* lm = sc.lm.as<LmDev>();
     hipLaunchKernelGGL(k_mapopt_pose, dim3(1), dim3(64), 0, st, 1, dp, dp + 8, dp + 16, lm, dp + 24);
     int* dsum = reinterpret_cast<int*>(dp + 32);
     hipLaunchKernelGGL(k_lm_finish, dim3(1), dim3(64), 0, st, lm, dp + 16, dsum);
+    if (win) {
+      // :481-493: the keyframe enters the window with the optimised pose on CONVERGENCE, else
+      // with the initial guess — the keyframe pose k_mapopt_pose selected
+      (void)lislam_mapwin_size(win, &nwin);
+      MCHK(c, hipMemcpyAsync(hwin, mapwin::info(win), sizeof(hwin), hipMemcpyDeviceToHost, st));
+      MRC(mapwin::push_staged(win, dp + 24));
+    }
     // Add_Points(downsample) of the voxelized cloud at the keyframe pose (:467-475)
     MCHK(c, m->newp.reserve((size_t)std::max(n, 1) * 16));
     hipLaunchKernelGGL(k_transform, dim3(blocks(n)), dim3(256), 0, st, voxbuf.as<float>(), 4, nvox, n, dp + 24,
@@ -1899,7 +1923,9 @@ int lislam_mapopt_step_corner(lislam_map* m, lislam_map* cm, const float* ground
     MCHK(c, hipMemcpyAsync(&hn, nvox, 4, hipMemcpyDeviceToHost, st));
     MCHK(c, hipMemcpyAsync(hs, dsum, 16, hipMemcpyDeviceToHost, st));
     MCHK(c, hipStreamSynchronize(st));
-    summ[0] = hs[3];
+    summ[3] = hwin[nwin * 6];  // kind-3 blocks count with the planes in the solve's summary
+    summ[4] = hwin[nwin * 6 + 1];
+    summ[0] = hs[3] - summ[3];
     summ[1] = hs[0];
     summ[2] = hs[1];
     hipLaunchKernelGGL(k_pack_points, dim3(blocks(hn)), dim3(256), 0, st, sc.vin.as<float>(), hn, 4, m->next_id,
@@ -1911,8 +1937,25 @@ int lislam_mapopt_step_corner(lislam_map* m, lislam_map* cm, const float* ground
     MCHK(c, hipMemcpyAsync(state, dp, 56, hipMemcpyDefault, st));
   }
   MCHK(c, hipStreamSynchronize(st));
-  if (summary) for (int e = 0; e < 3; e++) summary[e] = summ[e];
+  if (summary) for (int e = 0; e < nsum; e++) summary[e] = summ[e];
   return LISLAM_OK;
+}
+
+int lislam_mapopt_step_corner(lislam_map* m, lislam_map* cm, const float* ground, int32_t n, const float* corner,
+                              int32_t nc, const double* odom, double* state, double* out_pose, int32_t* summary) {
+  return mapopt_step_impl(m, cm, nullptr, ground, n, corner, nc, nullptr, nullptr, 0, odom, state, out_pose, summary, 3);
+}
+
+int lislam_mapopt_step_window(lislam_map* m, lislam_map* cm, lislam_mapwin* win, const float* ground, int32_t n,
+                              const float* corner, int32_t nc, const uint8_t* desc, const float* p3d, int32_t nf,
+                              const double* odom, double* state, double* out_pose, int32_t* summary) {
+  if (win && (!m || mapwin::context(win) != m->ctx)) return LISLAM_ERR_ARG;
+  if (win && (nf < 0 || (nf > 0 && (!desc || !p3d)))) return LISLAM_ERR_ARG;
+  if (win && nf > mapwin::feature_capacity(win))
+    return mfail(m->ctx, LISLAM_ERR_CAPACITY, "lislam_mapopt_step_window: %d features > feature_capacity %d", nf,
+                 mapwin::feature_capacity(win));
+  if (win && mapwin::window_size(win) == 0) win = nullptr;  // the window pops what it pushes (:491-493)
+  return mapopt_step_impl(m, cm, win, ground, n, corner, nc, desc, p3d, nf, odom, state, out_pose, summary, 5);
 }
 
 int lislam_laser_mapping(lislam_map* mc, lislam_map* ms, const float* corner, int32_t nc, const float* surf, int32_t ns,

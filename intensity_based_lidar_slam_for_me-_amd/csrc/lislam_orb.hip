@@ -142,6 +142,7 @@ struct Args {
   int* overflow;          // [1]
   const int* smap;        // scan of each grid scan index (null: identity from the slot base)
   const int* scount;      // device count of grid scan indices in use (null: all); the rest exit
+  int map_filter;         // k_orb_finish's zero filter: 0 feature tracker's, 1 mapOptimization's
 };
 
 __device__ __forceinline__ int reflect101(int p, int len) {
@@ -1262,7 +1263,10 @@ __device__ __forceinline__ void orb_finish_body(const Args& a, int gi) {
         o[1] *= g.scale[l];
         const int col = (int)rintf(o[0]), row = (int)rintf(o[1]);
         p = a.track[(size_t)s * g.W * g.H + row * g.W + col];
-        keep = !(fabsf(p.x) < 0.01f);
+        // extractPointsAndFilterZeroValue: intensity_feature_tracker.cpp drops on |x| alone,
+        // mapOptimization.cpp:620 only when all three axes are near zero (compared as doubles)
+        keep = a.map_filter ? !(fabs((double)p.x) < 0.01 && fabs((double)p.y) < 0.01 && fabs((double)p.z) < 0.01)
+                            : !(fabsf(p.x) < 0.01f);
       }
       int tot;
       const int rank = block_rank(sh, keep, &tot);
@@ -1929,6 +1933,7 @@ void features_per_level(int nfeatures, int* n) {
 struct OrbEngine {
   lislam_ctx* ctx = nullptr;
   int H = 0, W = 0, max_scans = 0, nfeatures = 0;
+  int map_filter = 0;  // Args::map_filter of every launch of this engine
   Geom g{};
   std::vector<void*> allocs;
   int *xo = nullptr, *yo = nullptr, *lim = nullptr;
@@ -1960,6 +1965,7 @@ struct OrbEngine {
     a.pyr = pyr; a.blur = blur; a.mpyr = mpyr; a.nms = nms; a.cand = cand; a.cresp = cresp;
     a.lkp = lkp; a.lcnt = lcnt; a.kp = kp; a.p3d = p3d; a.desc = desc; a.nkp = nkp; a.overflow = overflow;
     a.smap = nullptr;
+    a.map_filter = map_filter;
     return a;
   }
 };
@@ -2694,12 +2700,14 @@ int lislam_intensity_tracker_step(lislam_intensity_tracker* t, const uint8_t* im
 }
 
 // ---------------------------------------------------------------- building blocks
-int lislam_orb_detect(lislam_ctx* c, const uint8_t* image, const float* cloud_track, const uint8_t* mask, int32_t H,
-                      int32_t W, int32_t nfeatures, float* kp, uint8_t* desc, float* p3d, int32_t cap, int32_t* n) {
+static int orb_detect_impl(lislam_ctx* c, const uint8_t* image, const float* cloud_track, const uint8_t* mask, int32_t H,
+                           int32_t W, int32_t nfeatures, float* kp, uint8_t* desc, float* p3d, int32_t cap, int32_t* n,
+                           int map_filter) {
   if (!c || !image || !cloud_track || !n || H < 8 || W < 8 || nfeatures < 1 || nfeatures > 16384) return LISLAM_ERR_ARG;
   hipSetDevice(c->device);
   hipStream_t st = c->stream;
   OrbEngine e;
+  e.map_filter = map_filter;
   ORC(engine_init(&e, c, H, W, 1, nfeatures, mask));
   uint8_t* dimg = nullptr;
   float4* dtrk = nullptr;
@@ -2720,6 +2728,16 @@ int lislam_orb_detect(lislam_ctx* c, const uint8_t* image, const float* cloud_tr
   if (p3d) OCHK(c, hipMemcpyAsync(p3d, e.p3d, (size_t)cnt * 16, hipMemcpyDefault, st));
   OCHK(c, hipStreamSynchronize(st));
   return LISLAM_OK;
+}
+
+int lislam_orb_detect(lislam_ctx* c, const uint8_t* image, const float* cloud_track, const uint8_t* mask, int32_t H,
+                      int32_t W, int32_t nfeatures, float* kp, uint8_t* desc, float* p3d, int32_t cap, int32_t* n) {
+  return orb_detect_impl(c, image, cloud_track, mask, H, W, nfeatures, kp, desc, p3d, cap, n, 0);
+}
+
+int lislam_orb_detect_map(lislam_ctx* c, const uint8_t* image, const float* cloud_track, const uint8_t* mask, int32_t H,
+                          int32_t W, int32_t nfeatures, float* kp, uint8_t* desc, float* p3d, int32_t cap, int32_t* n) {
+  return orb_detect_impl(c, image, cloud_track, mask, H, W, nfeatures, kp, desc, p3d, cap, n, 1);
 }
 
 int lislam_orb_match(lislam_ctx* c, const uint8_t* qdesc, int32_t nq, const uint8_t* tdesc, int32_t nt, int32_t* matches,

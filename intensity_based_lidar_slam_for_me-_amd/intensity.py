@@ -36,8 +36,10 @@ def _vp(a):
     return None if a is None else ctypes.c_void_p(a.ctypes.data)
 
 
-def orb_detect(ctx, image, cloud_track, nfeatures: int = NUM_ORB_FEATURES, mask=None):
-    """detect + extractPointsAndFilterZeroValue + compute: (keypoints (n, 6), descriptors (n, 32), points (n, 4))."""
+def orb_detect(ctx, image, cloud_track, nfeatures: int = NUM_ORB_FEATURES, mask=None, map_filter: bool = False):
+    """detect + extractPointsAndFilterZeroValue + compute: (keypoints (n, 6), descriptors (n, 32), points (n, 4)).
+    map_filter: mapOptimization's variant of the zero filter (mapOptimization.cpp:604-632), which drops a
+    keypoint only when |x|, |y| and |z| of its point are all below 0.01 (lislam_orb_detect_map)."""
     img = _u8(image)
     H, W = img.shape
     tr = np.ascontiguousarray(cloud_track, np.float32).reshape(H * W, 4)
@@ -47,8 +49,9 @@ def orb_detect(ctx, image, cloud_track, nfeatures: int = NUM_ORB_FEATURES, mask=
     de = np.zeros((cap, 32), np.uint8)
     p3 = np.zeros((cap, 4), np.float32)
     n = ctypes.c_int32()
-    nat.check(ctx.lib.lislam_orb_detect(ctx.h, _vp(img), _vp(tr), _vp(m), H, W, nfeatures, nat.ptr(kp), nat.ptr(de),
-                                        nat.ptr(p3), cap, ctypes.byref(n)), ctx.h, "lislam_orb_detect")
+    fn = ctx.lib.lislam_orb_detect_map if map_filter else ctx.lib.lislam_orb_detect
+    nat.check(fn(ctx.h, _vp(img), _vp(tr), _vp(m), H, W, nfeatures, nat.ptr(kp), nat.ptr(de), nat.ptr(p3), cap,
+                 ctypes.byref(n)), ctx.h, "lislam_orb_detect_map" if map_filter else "lislam_orb_detect")
     return kp[: n.value], de[: n.value], p3[: n.value]
 
 

@@ -132,26 +132,125 @@ def voxel_grid(ctx, points, leaf: float) -> np.ndarray:
     return out[: n.value]
 
 
+class SlidingWindow:
+    """mapOptimization's keyframe_sliding_window_ (mapOptimization.cpp:155-169, :295-361, :481-493) on
+    the device (lislam_mapwin): keyframes of ORB descriptors (n, 32), their sensor-frame points (n, 4)
+    and a pose (q x,y,z,w, t)."""
+
+    KEEP = 820  # feature blocks per window keyframe at most: ceil(4096 * 0.2)
+
+    def __init__(self, ctx, window_size: int, feature_capacity: int = 4096):
+        self.ctx = ctx
+        self.window_size = window_size
+        self.feature_capacity = feature_capacity
+        h = ctypes.c_void_p()
+        nat.check(ctx.lib.lislam_mapwin_create(ctx.h, window_size, feature_capacity, ctypes.byref(h)), ctx.h,
+                  "lislam_mapwin_create")
+        self.h = h
+
+    def close(self):
+        if self.h:
+            self.ctx.lib.lislam_mapwin_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def _features(desc, p3d):
+        d = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+        p = np.ascontiguousarray(p3d, np.float32).reshape(-1, 4)
+        if d.shape[0] != p.shape[0]:
+            raise ValueError("descriptors and points differ in number")
+        return d, p
+
+    def __len__(self) -> int:
+        n = ctypes.c_int32()
+        nat.check(self.ctx.lib.lislam_mapwin_size(self.h, ctypes.byref(n)), self.ctx.h, "lislam_mapwin_size")
+        return n.value
+
+    def push(self, desc, p3d, pose):
+        """emplace_back, then pop_front beyond window_size."""
+        d, p = self._features(desc, p3d)
+        x = np.ascontiguousarray(pose, np.float64)
+        nat.check(self.ctx.lib.lislam_mapwin_push(self.h, nat.ptr(d), nat.ptr(p), d.shape[0], nat.ptr(x)), self.ctx.h,
+                  "lislam_mapwin_push")
+
+    def keyframe(self, index: int):
+        """Keyframe `index` (0 = oldest): (descriptors (n, 32), points (n, 4), pose (7,))."""
+        d = np.zeros((self.feature_capacity, 32), np.uint8)
+        p = np.zeros((self.feature_capacity, 4), np.float32)
+        x = np.zeros(7)
+        n = ctypes.c_int32()
+        nat.check(self.ctx.lib.lislam_mapwin_keyframe(self.h, index, nat.ptr(d), nat.ptr(p), self.feature_capacity,
+                                                      ctypes.byref(n), nat.ptr(x)), self.ctx.h, "lislam_mapwin_keyframe")
+        return d[: n.value].copy(), p[: n.value].copy(), x
+
+    def match(self, desc) -> np.ndarray:
+        """BFMatcher(NORM_L2).match against every keyframe, newest first: (len(self), n, 2) = train
+        index, integer squared distance (-1, -1 against an empty keyframe)."""
+        d = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+        out = np.zeros((max(len(self), 1), max(d.shape[0], 1), 2), np.int32)
+        nat.check(self.ctx.lib.lislam_mapwin_match(self.h, nat.ptr(d), d.shape[0], nat.ptr(out)), self.ctx.h,
+                  "lislam_mapwin_match")
+        return out[: len(self), : d.shape[0]]
+
+    def records(self, desc, p3d, pose):
+        """The window loop (:295-361) for a current keyframe at `pose`: (records (n, 9), info
+        (len(self), 6) = train descriptors, M, G, used, blocks kept, first block; pairs (n, 3) =
+        window row (0 = newest), query index, train index)."""
+        d, p = self._features(desc, p3d)
+        x = np.ascontiguousarray(pose, np.float64)
+        cap = max(self.window_size, 1) * self.KEEP
+        rec = np.zeros((cap, 9))
+        info = np.zeros((max(self.window_size, 1), 6), np.int32)
+        pairs = np.zeros((cap, 3), np.int32)
+        n = ctypes.c_int32()
+        nat.check(self.ctx.lib.lislam_mapwin_records(self.h, nat.ptr(d), nat.ptr(p), d.shape[0], nat.ptr(x), nat.ptr(rec),
+                                                     cap, ctypes.byref(n), nat.ptr(info), nat.ptr(pairs)), self.ctx.h,
+                  "lislam_mapwin_records")
+        return rec[: n.value], info[: len(self)], pairs[: n.value]
+
+
 class MapOptimization:
     """Ground-map stage of the mapOptimization node (ikd-Tree map of downsample 0.4,
     mapOptimization.cpp:504) and, with corner=True, its corner ikd-Tree (downsample 0.8,
-    :505), which takes pc_corner at the same keyframe pose (:193-195, :477-479)."""
+    :505), which takes pc_corner at the same keyframe pose (:193-195, :477-479).  With
+    sliding_window_size > 0 (config sliding_window_size; the reference recommends 10 or 5) the ORB
+    features of each keyframe are matched against a window of earlier keyframes and join the
+    optimisation as FeatureMatchingResiduals (:295-361); summaries then have five entries
+    (planes, iterations, termination, feature blocks, window keyframes used)."""
 
     def __init__(self, ctx, downsample_size: float = 0.4, cell_size: float = 0.0, corner: bool = False,
-                 corner_downsample: float = 0.8):
+                 corner_downsample: float = 0.8, sliding_window_size: int = 0, feature_capacity: int = 4096):
         self.map = IkdMap(ctx, downsample_size, cell_size)
         self.corner_map = IkdMap(ctx, corner_downsample, cell_size) if corner else None
+        self.window = SlidingWindow(ctx, sliding_window_size, feature_capacity) if sliding_window_size > 0 else None
         self.state = np.array([0, 0, 0, 1, 0, 0, 0], np.float64)  # q_wmap_wodom, t_wmap_wodom
 
-    def callback(self, ground, odom, pc_corner=None):
+    def callback(self, ground, odom, pc_corner=None, features=None):
         """One frame: ground = GroundPointOut (sensor frame, (n, 4)), odom = q_wodom_curr, t_wodom_curr,
-        pc_corner = the corner cloud (sensor frame, (m, 4); with corner=True).
+        pc_corner = the corner cloud (sensor frame, (m, 4); with corner=True), features = (descriptors
+        (n, 32), points (n, 4)) of the keyframe's ORB features (with sliding_window_size > 0).
         Returns (q_w_curr, t_w_curr (7,), summary (planes, iterations, termination; -1 = built))."""
         g = np.ascontiguousarray(ground, np.float32).reshape(-1, 4)
         od = np.ascontiguousarray(odom, np.float64)
         pose = np.zeros(7)
         summ = np.zeros(3, np.int32)
         ctx = self.map.ctx
+        if self.window is not None:
+            d, p = SlidingWindow._features(*(features if features is not None else (np.zeros((0, 32)), np.zeros((0, 4)))))
+            c = np.ascontiguousarray(pc_corner if pc_corner is not None else np.zeros((0, 4)), np.float32).reshape(-1, 4)
+            summ = np.zeros(5, np.int32)
+            cm = self.corner_map.h if self.corner_map is not None else None
+            nat.check(ctx.lib.lislam_mapopt_step_window(self.map.h, cm, self.window.h, nat.ptr(g), g.shape[0], nat.ptr(c),
+                                                        c.shape[0] if cm else 0, nat.ptr(d), nat.ptr(p), d.shape[0],
+                                                        nat.ptr(od), nat.ptr(self.state), nat.ptr(pose), nat.ptr(summ)),
+                      ctx.h, "lislam_mapopt_step_window")
+            return pose, summ
         if self.corner_map is None:
             nat.check(ctx.lib.lislam_mapopt_step(self.map.h, nat.ptr(g), g.shape[0], nat.ptr(od), nat.ptr(self.state),
                                                  nat.ptr(pose), nat.ptr(summ)), ctx.h, "lislam_mapopt_step")
@@ -179,15 +278,28 @@ class MapOptimization:
         tq = qmul(qmul(qm, np.array([to[0], to[1], to[2], 0.0])), qm * np.array([-1, -1, -1, 1.0]))[:3]
         return np.concatenate([qw, tq + tm])
 
-    def callback_batch(self, batch, scan: int, odom):
+    def callback_batch(self, batch, scan: int, odom, nfeatures=None, mask=None):
         """The same frame fed from a batch on the device: GroundPointOut of `scan` (batch.ground
         first) + its less-flat cloud, as mapOptimizationCallback assembles them (:136-150); with
-        corner=True the scan's less-sharp cloud is pc_corner (mapOptimizationNode.cpp:63)."""
+        corner=True the scan's less-sharp cloud is pc_corner (mapOptimizationNode.cpp:63).  With
+        sliding_window_size > 0 the scan's ORB features (cv::ORB::create(nfeatures, ...), :155; mask
+        (H, W) uint8 or None) are detected on the device from its intensity image and cloud_track
+        (the context's want_images) and stay there."""
         od = np.ascontiguousarray(odom, np.float64)
         pose = np.zeros(7)
         summ = np.zeros(3, np.int32)
         ctx = self.map.ctx
         cm = self.corner_map.h if self.corner_map is not None else None
+        if self.window is not None:
+            if nfeatures is None:
+                raise ValueError("callback_batch with a sliding window needs nfeatures (NUM_ORB_FEATURES * 2)")
+            mk = None if mask is None else np.ascontiguousarray(mask, np.uint8)
+            summ = np.zeros(5, np.int32)
+            nat.check(ctx.lib.lislam_batch_mapopt_window(batch.h, self.map.h, cm, self.window.h, scan, int(nfeatures),
+                                                         None if mk is None else nat.ptr(mk), nat.ptr(od),
+                                                         nat.ptr(self.state), nat.ptr(pose), nat.ptr(summ)), ctx.h,
+                      "lislam_batch_mapopt_window")
+            return pose, summ
         nat.check(ctx.lib.lislam_batch_mapopt_corner(batch.h, self.map.h, cm, scan, nat.ptr(od), nat.ptr(self.state),
                                                      nat.ptr(pose), nat.ptr(summ)), ctx.h, "lislam_batch_mapopt_corner")
         return pose, summ
@@ -196,6 +308,8 @@ class MapOptimization:
         self.map.close()
         if self.corner_map is not None:
             self.corner_map.close()
+        if self.window is not None:
+            self.window.close()
 
 
 def laser_mapping(corner_map: IkdMap, surf_map: IkdMap, corner, surf, x0):

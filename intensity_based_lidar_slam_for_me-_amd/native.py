@@ -56,12 +56,15 @@ EXPORTED_SYMBOLS = (
     "lislam_pgo_create", "lislam_pgo_destroy", "lislam_pgo_size", "lislam_pgo_add_nodes", "lislam_pgo_set_prior",
     "lislam_pgo_add_edges", "lislam_pgo_add_batch", "lislam_pgo_edges", "lislam_pgo_linearize", "lislam_pgo_optimize",
     "lislam_pgo_poses",
+    "lislam_mapwin_create", "lislam_mapwin_destroy", "lislam_mapwin_size", "lislam_mapwin_push", "lislam_mapwin_keyframe",
+    "lislam_mapwin_match", "lislam_mapwin_records", "lislam_mapopt_step_window", "lislam_orb_detect_map",
+    "lislam_batch_mapopt_window",
 )
 
 MAP_KERNELS = ("k_knn", "k_fit", "k_lm_eval", "k_lm_step", "map_rebuild", "map_downsample", "k_orb_pyramid",
                "k_orb_fast", "k_orb_select", "k_orb_finish", "k_orb_blur", "k_orb_desc", "k_orb_match", "k_orb_lm",
                "k_ground_screen", "k_ground_ransac", "k_ground_extract", "k_lc_step", "k_lc_apply", "k_fuse",
-               "k_orb_roiblur", "k_lm_solve")
+               "k_orb_roiblur", "k_lm_solve", "k_mw_match", "k_mw_select", "k_mw_gate")
 
 MATCH_LINE, MATCH_PLANE = 0, 1
 PLACE_DESC, PLACE_RING_KEY, PLACE_SECTOR_KEY = 0, 1, 2
@@ -320,6 +323,16 @@ def load(path: str = LIB_PATH):
     L.lislam_pgo_linearize.argtypes = [vp, vp, vp, vp, vp, vp]
     L.lislam_pgo_optimize.argtypes = [vp, vp, vp]
     L.lislam_pgo_poses.argtypes = [vp, _i32, _i32, vp, vp]
+    L.lislam_mapwin_create.argtypes = [vp, _i32, _i32, ctypes.POINTER(vp)]
+    L.lislam_mapwin_destroy.argtypes = [vp]
+    L.lislam_mapwin_size.argtypes = [vp, _i32p]
+    L.lislam_mapwin_push.argtypes = [vp, vp, vp, _i32, vp]
+    L.lislam_mapwin_keyframe.argtypes = [vp, _i32, vp, vp, _i32, _i32p, vp]
+    L.lislam_mapwin_match.argtypes = [vp, vp, _i32, vp]
+    L.lislam_mapwin_records.argtypes = [vp, vp, vp, _i32, vp, vp, _i32, _i32p, vp, vp]
+    L.lislam_mapopt_step_window.argtypes = [vp, vp, vp, vp, _i32, vp, _i32, vp, vp, _i32, vp, vp, vp, vp]
+    L.lislam_orb_detect_map.argtypes = [vp, vp, vp, vp, _i32, _i32, _i32, vp, vp, vp, _i32, _i32p]
+    L.lislam_batch_mapopt_window.argtypes = [vp, vp, vp, vp, _i32, _i32, vp, vp, vp, vp, vp]
     L.lislam_map_set_timing.argtypes = [vp, _i32]
     L.lislam_map_kernel_times.argtypes = [vp, _fp, _i32p]
     for name in EXPORTED_SYMBOLS:
