@@ -47,6 +47,8 @@
  *   lislam_bow_train(er_*)    <- DBoW3::Vocabulary::create: the tree    src/loop_closure_handler.cpp:12-17 loads from a file
  *   lislam_pgo_*              <- the gtsam factor graph + updatePoses  src/intensity_feature_tracker.cpp:110-145,
  *                                                                      :314-381, :395-583
+ *   lislam_keysel_*           <- feature_tracker::getKeyframe          src/intensity_feature_tracker.cpp:741-815
+ *   (lislam_feeds.h)          <- the same feeds for a list of selected scans; mapOdomHandle's keyframe-to-keyframe edges :395-514
  */
 #ifndef LISLAM_H_
 #define LISLAM_H_
@@ -870,6 +872,48 @@ int lislam_pgo_optimize(lislam_pgo* p, int32_t* info, double* stats);
  * PointTypePose that getTransformMatrix (:152-165) turns back into the node's matrix: it builds
  * RzRyRx(yaw, pitch, roll), so roll is the angle about z and yaw the one about x (|pitch| < pi / 2). */
 int lislam_pgo_poses(lislam_pgo* p, int32_t first, int32_t n, double* pose7, float* pose6d);
+
+/* ---- Keyframe selection: feature_tracker::getKeyframe (src/intensity_feature_tracker.cpp:741-815, called
+ * at :721) behind tfBroadcast's T_s2m_ = T_s2m_ * T_s2s_ (:819), the join between the per-scan ORB front
+ * end and the back end's pools.  State (ctor :31-37), device resident: T_s2m = I, prev_p = 0, prev_R = 0,
+ * next id 0, no keyframe yet.  For frame k, in stream order:
+ *   T_s2m = T_s2m * [R(q) t; 0 0 0 1]   every frame, the identity of a skipped frame (:728) too; R(q) by
+ *                                       Eigen's toRotationMatrix formula, the 4x4 product entry by entry as
+ *                                       ((a0 b0 + a1 b1) + a2 b2) + a3 b3, plain double, no FMA
+ *   good[k] != 1: keyframe_id[k] = -1   getKeyframe is called on good frames only (:693, :721)
+ *   p, R = T_s2m's translation and rotation; the frame is selected iff no keyframe exists yet, or
+ *   time[k] - last_time > time_interval and |p - prev_p| > distance_interval (:774-777, both strict);
+ *   then node = (time[k], id, p, prev_p, R, prev_R), keyframe_id[k] = id, last_time = time[k],
+ *   prev_p = p, prev_R = R, id += 1.
+ * Decision: the reference's first branch tests cloudKeyPoses3D_->points.empty() (:749), a container
+ * another thread fills (:536), so the number of frames that take it depends on scheduling there.  Here it
+ * is taken exactly once, by the first good frame of the selector's life.
+ * Two calls over the halves of a stream give what one call over the whole stream gives.
+ * include/lislam_feeds.h declares the forms of the back end's feeds that take the selected scans as a list. */
+typedef struct lislam_keysel lislam_keysel;
+typedef struct {
+  double time_interval;     /* KEYFRAME_TIME_INTERVAL: config/spot.yaml:35 has 0.3; readParameters' own default is 15 (:1120) */
+  double distance_interval; /* KEYFRAME_DISTANCE_INTERVAL (0.3; "outdoor: 3") */
+} lislam_keysel_config;
+/* cfg == NULL: 0.3, 0.3.  A NaN interval is LISLAM_ERR_ARG. */
+int lislam_keysel_create(lislam_ctx* ctx, const lislam_keysel_config* cfg, lislam_keysel** out);
+int lislam_keysel_destroy(lislam_keysel* s);
+/* n frames in stream order.  T_s2s[n][7] (q x,y,z,w, t) and good[n]: host or device memory; time[n]: host.
+ * Outputs (host, each nullable): keyframe_id[n] (-1 = not a keyframe), *n_selected, T_s2m[n][16] row-major
+ * after each frame, node[n][26] of which the first *n_selected rows are written, one per keyframe in
+ * order: time, id, cur_position_[3], prev_position_[3], cur_rotation_[9], prev_rotation_[9], the
+ * rotations row-major (FactorGraphNode, src/keyframe.h:115-121).  n == 0 is a no-op (*n_selected = 0). */
+int lislam_keysel_step(lislam_keysel* s, const double* T_s2s, const int32_t* good, const double* time, int32_t n,
+                       int32_t* keyframe_id, int32_t* n_selected, double* T_s2m, double* node);
+/* The same for scans [first_scan, first_scan + n_scans) of a batch: each scan's LISLAM_OUT_ORB_T row and
+ * its LISLAM_OUT_ORB_STATS[0] (good means == 1) are read where they lie on the device, after a pending
+ * device-decided cascade has settled.  LISLAM_ERR_STATE unless lislam_batch_intensity_odometry has run
+ * over those scans; the other error codes as lislam_place_add_batch. */
+int lislam_keysel_step_batch(lislam_keysel* s, lislam_batch* b, int32_t first_scan, int32_t n_scans, const double* time,
+                             int32_t* keyframe_id, int32_t* n_selected, double* T_s2m, double* node);
+/* Each nullable: the keyframes selected so far, T_s2m (row-major 4x4), the last keyframe's time (NaN
+ * before the first). */
+int lislam_keysel_state(lislam_keysel* s, int32_t* n_keyframes, double* T_s2m16, double* last_time);
 
 /* HIP-event timing of the mapping kernels of a context (recorded on its stream, no host sync
  * while recording).  lislam_map_kernel_times synchronizes, returns the total ms and launch count

@@ -82,6 +82,13 @@ class BowDatabase:
         intensity_odometry has run, on the device."""
         nat.check(self.ctx.lib.lislam_bow_add_batch(self.h, batch.h, int(first), int(n)), self.ctx.h, "lislam_bow_add_batch")
 
+    def add_batch_scans(self, batch, scans) -> None:
+        """The ORB descriptors of the listed scans of a batch whose intensity_odometry has run (any order,
+        repeats allowed) in one set of launches: what ``add_batch(batch, s, 1)`` for every s would leave."""
+        s = np.ascontiguousarray(np.atleast_1d(scans), np.int32).reshape(-1)
+        nat.check(self.ctx.lib.lislam_bow_add_batch_scans(self.h, batch.h, nat.ptr(s) if s.size else None, s.shape[0]),
+                  self.ctx.h, "lislam_bow_add_batch_scans")
+
     def detect(self, first: int | None = None, n: int | None = None) -> Detection:
         """detectLoop as it returned when keyframe k was the newest, k in [first, first + n)
         (default: every keyframe), with the results of the query behind it."""

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "../../include/lislam.h"
+#include "../../include/lislam_feeds.h"
 #include "lislam_internal.hpp"
 
 using lislam::FeatureArgs;

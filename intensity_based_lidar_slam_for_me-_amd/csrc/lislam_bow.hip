@@ -66,6 +66,16 @@ struct Source {
   int n_images, per_image, max_count;
 };
 
+// lislam_bow_add_batch_scans: image k = scan scans[k] of a batch, as the packed form's (offset, count) pair.
+__global__ __launch_bounds__(kThreads) void k_bow_scan_list(const int* __restrict__ scans, int n, const int* __restrict__ counts,
+                                                            int cap, long long* __restrict__ off, int* __restrict__ cnt) {
+  const int k = blockIdx.x * kThreads + threadIdx.x;
+  if (k >= n) return;
+  const int s = scans[k];
+  off[k] = (long long)s * cap;
+  cnt[k] = counts[s];
+}
+
 template <int kLanes>
 __device__ __forceinline__ uint32_t group_umin(uint32_t v) {
   if constexpr (kLanes == 64) {
@@ -662,6 +672,42 @@ int lislam_bow_add_batch(lislam_bow* p, lislam_batch* b, int32_t first_scan, int
   // a scan keeps at most nfeatures keypoints; max_count bounds the rows read whatever the count says
   Source src{reinterpret_cast<const uint4*>(desc + (size_t)first_scan * cap * 32), nullptr, counts + first_scan, cap, n_scans,
              std::min(nfeatures, cap), std::min(nfeatures, cap)};
+  return add_images(p, src);
+}
+
+int lislam_bow_add_batch_scans(lislam_bow* p, lislam_batch* b, const int32_t* scans, int32_t n) {
+  if (!p || !b || n < 0 || (n > 0 && !scans)) return LISLAM_ERR_ARG;
+  lislam_ctx* c = p->ctx;
+  if (b->ctx != c) return bfail(c, LISLAM_ERR_ARG, "lislam_bow_add_batch_scans: the batch belongs to another context");
+  const uint8_t* desc = nullptr;
+  const int* counts = nullptr;
+  int cap = 0, nfeatures = 0, ran = 0;
+  int rc = lislam_orb_batch_descriptors(b, &desc, &counts, &cap, &nfeatures, &ran);
+  if (rc == LISLAM_ERR_STATE)
+    return bfail(c, LISLAM_ERR_STATE, "lislam_bow_add_batch_scans: run lislam_batch_intensity_odometry first");
+  if (rc) return rc;
+  for (int k = 0; k < n; k++)
+    if (scans[k] < 0 || scans[k] >= ran)
+      return bfail(c, LISLAM_ERR_ARG, "lislam_bow_add_batch_scans: scans[%d] = %d outside [0, %d)", k, scans[k], ran);
+  if (nfeatures > p->F)
+    return bfail(c, LISLAM_ERR_ARG, "lislam_bow_add_batch_scans: the batch detects %d features, max_features is %d", nfeatures,
+                 p->F);
+  if ((int64_t)p->n + n > p->capacity)
+    return bfail(c, LISLAM_ERR_CAPACITY, "lislam_bow_add_batch_scans: %d + %d entries exceed the capacity %d", p->n, n,
+                 p->capacity);
+  if (n == 0) return LISLAM_OK;
+  hipSetDevice(c->device);
+  // [offsets long long n][counts int n][scans int n]
+  if ((rc = reserve(c, &p->meta, &p->meta_bytes, (size_t)n * (sizeof(long long) + 2 * sizeof(int))))) return rc;
+  long long* d_off = static_cast<long long*>(p->meta);
+  int* d_cnt = reinterpret_cast<int*>(d_off + n);
+  int* d_scans = d_cnt + n;
+  // pageable source: the copy has read it when it returns
+  BCHK(c, hipMemcpyAsync(d_scans, scans, (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  hipLaunchKernelGGL(k_bow_scan_list, dim3((n + kThreads - 1) / kThreads), dim3(kThreads), 0, c->stream, d_scans, n, counts, cap,
+                     d_off, d_cnt);
+  // as the range form: max_count bounds the rows read whatever the count says
+  Source src{reinterpret_cast<const uint4*>(desc), d_off, d_cnt, 0, n, std::min(nfeatures, cap), std::min(nfeatures, cap)};
   return add_images(p, src);
 }
 

@@ -3213,6 +3213,17 @@ __global__ __launch_bounds__(kRed) void k_lv_fitness(IcpDev* st, const LvCand* c
   lc_fitness_body(st + blockIdx.x, d2 + C.w_off, found + C.w_off, C.ns, red);
 }
 
+// lislam_keyframes_add_batch_scans: cloud k of the output = scan scans[k] of the batch's cloud_track
+// (N points each), 16 bytes per lane and access; blockIdx.y = k, the parts of a cloud interleave by
+// workgroup-sized runs.
+constexpr int kGather = 256;
+__global__ __launch_bounds__(kGather) void k_kf_gather(const float4* __restrict__ track, const int* __restrict__ scans, int N,
+                                                       float4* __restrict__ out) {
+  const float4* src = track + (size_t)scans[blockIdx.y] * N;
+  float4* dst = out + (size_t)blockIdx.y * N;
+  for (int i = blockIdx.x * kGather + threadIdx.x; i < N; i += gridDim.x * kGather) dst[i] = src[i];
+}
+
 }  // namespace loopk
 }  // namespace lislam
 
@@ -3222,6 +3233,7 @@ struct lislam_keyframes {
   int64_t point_capacity = 0;
   float4* pts = nullptr;
   std::vector<int64_t> off{0};  // keyframe i = pts[off[i], off[i + 1])
+  DBuf list;                    // the scan list of lislam_keyframes_add_batch_scans
   int32_t size() const { return (int32_t)off.size() - 1; }
 };
 
@@ -3348,6 +3360,38 @@ int lislam_keyframes_add_batch(lislam_keyframes* kf, lislam_batch* b, int32_t fi
   MCHK(c, hipMemcpyAsync(kf->pts + kf->off.back(), reinterpret_cast<const float4*>(b->fa.track) + (size_t)first_scan * b->N,
                          (size_t)total * sizeof(float4), hipMemcpyDeviceToDevice, stream_of(c)));
   for (int k = 0; k < n_scans; k++) kf->off.push_back(kf->off.back() + b->N);
+  return LISLAM_OK;
+}
+
+int lislam_keyframes_add_batch_scans(lislam_keyframes* kf, lislam_batch* b, const int32_t* scans, int32_t n) {
+  if (!kf || !b || n < 0 || (n > 0 && !scans)) return LISLAM_ERR_ARG;
+  lislam_ctx* c = kf->ctx;
+  if (b->ctx != c) return mfail(c, LISLAM_ERR_ARG, "lislam_keyframes_add_batch_scans: the batch belongs to another context");
+  if (!b->fa.track)
+    return mfail(c, LISLAM_ERR_STATE, "lislam_keyframes_add_batch_scans: cloud_track not materialized (want_images=0)");
+  if (n > 0 && b->extracted < 1) return mfail(c, LISLAM_ERR_STATE, "lislam_keyframes_add_batch_scans: extract the batch first");
+  for (int k = 0; k < n; k++)
+    if (scans[k] < 0 || scans[k] >= b->extracted)
+      return mfail(c, LISLAM_ERR_ARG, "lislam_keyframes_add_batch_scans: scans[%d] = %d outside [0, %d)", k, scans[k],
+                   b->extracted);
+  if ((int64_t)kf->size() + n > kf->capacity)
+    return mfail(c, LISLAM_ERR_CAPACITY, "lislam_keyframes_add_batch_scans: %d + %d keyframes exceed the capacity %d", kf->size(),
+                 n, kf->capacity);
+  const int64_t total = (int64_t)n * b->N;
+  if (kf->off.back() + total > kf->point_capacity)
+    return mfail(c, LISLAM_ERR_CAPACITY, "lislam_keyframes_add_batch_scans: %lld + %lld points exceed the capacity %lld",
+                 (long long)kf->off.back(), (long long)total, (long long)kf->point_capacity);
+  if (n == 0) return LISLAM_OK;
+  hipSetDevice(c->device);
+  MCHK(c, kf->list.reserve((size_t)n * sizeof(int)));
+  // pageable source: the copy has read it when it returns
+  MCHK(c, hipMemcpyAsync(kf->list.p, scans, (size_t)n * sizeof(int), hipMemcpyHostToDevice, stream_of(c)));
+  const int parts = std::max(1, std::min(64, (b->N + 4 * loopk::kGather - 1) / (4 * loopk::kGather)));
+  hipLaunchKernelGGL(loopk::k_kf_gather, dim3(parts, n), dim3(loopk::kGather), 0, stream_of(c),
+                     reinterpret_cast<const float4*>(b->fa.track), static_cast<const int*>(kf->list.p), b->N,
+                     kf->pts + kf->off.back());
+  MCHK(c, hipGetLastError());
+  for (int k = 0; k < n; k++) kf->off.push_back(kf->off.back() + b->N);
   return LISLAM_OK;
 }
 

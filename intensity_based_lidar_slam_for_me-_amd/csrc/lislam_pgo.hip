@@ -670,6 +670,42 @@ __global__ __launch_bounds__(kThreads) void k_pgo_add_batch(int n, int k0, const
   for (int e = 0; e < 6; e++) sigma[(size_t)id * 6 + e] = sig6[e];
 }
 
+// lislam_pgo_add_keyframes: keyframe k = pose[index[k]] becomes node base + k (the row, byte for byte);
+// edge ebase + k - k0 measures prev^-1 pose[index[k]], prev = pose[index[k-1]], for k = 0 the pose the
+// graph's last node was added with (k0 = 1 when the graph was empty).  The last keyframe's row is
+// left in added_out for the next call (another buffer than added_in: thread 0 reads that one).
+__global__ __launch_bounds__(kThreads) void k_pgo_add_keyframes(int n, int k0, const double* __restrict__ pose,
+                                                                const int* __restrict__ index,
+                                                                const double* __restrict__ added_in,
+                                                                double* __restrict__ added_out, int base, int ebase,
+                                                                double* __restrict__ x, int* __restrict__ from,
+                                                                int* __restrict__ to, double* __restrict__ meas,
+                                                                double* __restrict__ sigma, int* __restrict__ robust,
+                                                                const double* __restrict__ sig6) {
+  const int k = blockIdx.x * kThreads + threadIdx.x;
+  if (k >= n) return;
+  const double* cur = pose + (size_t)index[k] * 7;
+#pragma unroll
+  for (int e = 0; e < 7; e++) x[(size_t)(base + k) * 7 + e] = cur[e];
+  if (k == n - 1) {
+#pragma unroll
+    for (int e = 0; e < 7; e++) added_out[e] = cur[e];
+  }
+  if (k < k0) return;
+  const int id = ebase + k - k0;
+  const double* prev = k > 0 ? pose + (size_t)index[k - 1] * 7 : added_in;
+  const Pose z = between(load_pose(prev), load_pose(cur));
+  from[id] = base + k - 1;
+  to[id] = base + k;
+  robust[id] = 0;
+#pragma unroll
+  for (int e = 0; e < 4; e++) meas[(size_t)id * 7 + e] = z.q[e];
+#pragma unroll
+  for (int e = 0; e < 3; e++) meas[(size_t)id * 7 + 4 + e] = z.t[e];
+#pragma unroll
+  for (int e = 0; e < 6; e++) sigma[(size_t)id * 6 + e] = sig6[e];
+}
+
 // PointTypePose of each node as getTransformMatrix (:152-165) reads it back: R = Rz(roll) Ry(pitch) Rx(yaw).
 __global__ __launch_bounds__(kThreads) void k_pgo_pose6d(int n, const double* __restrict__ x, float* __restrict__ out) {
   const int k = blockIdx.x * kThreads + threadIdx.x;
@@ -701,6 +737,13 @@ struct lislam_pgo {
   int cur = 0;
   int *from = nullptr, *to = nullptr, *robust = nullptr;
   double *meas = nullptr, *sigma = nullptr, *prior = nullptr, *odom_sigma = nullptr;
+  // the pose the last node was added with (graph_prev_rotation_ / graph_prev_translation_, :513-514):
+  // added[added_cur]; lislam_pgo_add_keyframes reads it and writes the other one
+  double* added[2] = {nullptr, nullptr};
+  int added_cur = 0;
+  // grow-only staging of lislam_pgo_add_keyframes: [pose7 n_poses x 7][index n]
+  void* kstage = nullptr;
+  size_t kstage_bytes = 0;
   int *adj_off = nullptr, *adj = nullptr;
   Blocks b{};
   double *Hd = nullptr, *U = nullptr, *g = nullptr, *Sinv = nullptr, *L = nullptr;
@@ -746,6 +789,7 @@ bool dalloc(lislam_pgo* p, T** out, size_t count) {
 void free_pgo(lislam_pgo* p) {
   for (void* q : p->allocs) (void)hipFree(q);
   if (p->h_res) (void)hipHostFree(p->h_res);
+  if (p->kstage) (void)hipFree(p->kstage);
   delete p;
 }
 
@@ -815,7 +859,7 @@ int lislam_pgo_create(lislam_ctx* c, const lislam_pgo_config* cfg, int32_t node_
   const size_t N = (size_t)node_capacity, E = (size_t)edge_capacity;
   bool ok = dalloc(p, &p->x[0], N * 7) && dalloc(p, &p->x[1], N * 7) && dalloc(p, &p->from, E) && dalloc(p, &p->to, E) &&
             dalloc(p, &p->robust, E) && dalloc(p, &p->meas, E * 7) && dalloc(p, &p->sigma, E * 6) && dalloc(p, &p->prior, 13) &&
-            dalloc(p, &p->odom_sigma, 6) && dalloc(p, &p->adj_off, N + 1) && dalloc(p, &p->adj, 2 * E + 1) &&
+            dalloc(p, &p->odom_sigma, 6) && dalloc(p, &p->added[0], 7) && dalloc(p, &p->added[1], 7) && dalloc(p, &p->adj_off, N + 1) && dalloc(p, &p->adj, 2 * E + 1) &&
             dalloc(p, &p->b.Af, E * 36) && dalloc(p, &p->b.At, (E + 1) * 36) && dalloc(p, &p->b.W, E * 36) &&
             dalloc(p, &p->b.bf, E * 6) && dalloc(p, &p->b.bt, (E + 1) * 6) && dalloc(p, &p->b.wt, E + 1) &&
             dalloc(p, &p->b.term, E + 1) && dalloc(p, &p->Hd, N * 36) && dalloc(p, &p->U, N * 36) && dalloc(p, &p->g, N * 6) &&
@@ -859,6 +903,8 @@ int lislam_pgo_add_nodes(lislam_pgo* p, const double* pose7, int32_t n) {
     if (!finite_pose(pose7 + (size_t)k * 7)) return gfail(c, LISLAM_ERR_ARG, "lislam_pgo_add_nodes: pose %d is not finite", k);
   hipSetDevice(c->device);
   GCHK(c, hipMemcpyAsync(p->x[p->cur] + (size_t)p->n * 7, pose7, (size_t)n * 7 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  GCHK(c, hipMemcpyAsync(p->added[p->added_cur], pose7 + (size_t)(n - 1) * 7, 7 * sizeof(double), hipMemcpyHostToDevice,
+                         c->stream));
   GCHK(c, hipStreamSynchronize(c->stream));
   p->n += n;
   p->adj_dirty = true;
@@ -941,6 +987,8 @@ int lislam_pgo_add_batch(lislam_pgo* p, lislam_batch* b, int32_t first_scan, int
                      b->oa.pose + (size_t)first_scan * 7, p->n, p->e, p->x[p->cur], p->from, p->to, p->meas, p->sigma, p->robust,
                      p->odom_sigma);
   GCHK(c, hipGetLastError());
+  GCHK(c, hipMemcpyAsync(p->added[p->added_cur], b->oa.pose + (size_t)(first_scan + n_scans - 1) * 7, 7 * sizeof(double),
+                         hipMemcpyDeviceToDevice, c->stream));
   for (int k = k0; k < n_scans; k++) {
     p->h_from.push_back(p->n + k - 1);
     p->h_to.push_back(p->n + k);
@@ -949,6 +997,94 @@ int lislam_pgo_add_batch(lislam_pgo* p, lislam_batch* b, int32_t first_scan, int
   p->e += n_edges;
   p->adj_dirty = true;
   return LISLAM_OK;
+}
+
+namespace {
+
+// The body of lislam_pgo_add_keyframes / lislam_pgo_add_batch_scans once the arguments are checked:
+// d_pose = the trajectory on the device (null: stage pose7 first), index = the host list.
+int add_keyframes(lislam_pgo* p, const char* who, const double* d_pose, const double* pose7, int n_poses, const int32_t* index,
+                  int n, const double* var6) {
+  lislam_ctx* c = p->ctx;
+  const int k0 = p->n > 0 ? 0 : 1;
+  const int n_edges = n - k0;
+  if ((int64_t)p->n + n > p->ncap || (int64_t)p->e + n_edges > p->ecap)
+    return gfail(c, LISLAM_ERR_CAPACITY, "%s: %d + %d nodes / %d + %d edges exceed the capacity %d / %d", who, p->n, n, p->e,
+                 n_edges, p->ncap, p->ecap);
+  hipSetDevice(c->device);
+  const size_t staged = d_pose ? 0 : (size_t)n_poses * 7 * sizeof(double);
+  const size_t want = staged + (size_t)n * sizeof(int);
+  if (want > p->kstage_bytes) {
+    if (p->kstage) {
+      GCHK(c, hipStreamSynchronize(c->stream));
+      (void)hipFree(p->kstage);
+      p->kstage = nullptr;
+      p->kstage_bytes = 0;
+    }
+    GCHK(c, hipMalloc(&p->kstage, want));
+    p->kstage_bytes = want;
+  }
+  int* d_index = reinterpret_cast<int*>(static_cast<char*>(p->kstage) + staged);
+  double sg[6];
+  for (int k = 0; k < 6; k++) sg[k] = std::sqrt(var6 ? var6[k] : kOdometryVariances[k]);
+  if (!d_pose) {
+    GCHK(c, hipMemcpyAsync(p->kstage, pose7, staged, hipMemcpyDefault, c->stream));
+    d_pose = static_cast<const double*>(p->kstage);
+  }
+  GCHK(c, hipMemcpyAsync(d_index, index, (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  GCHK(c, hipMemcpyAsync(p->odom_sigma, sg, sizeof(sg), hipMemcpyHostToDevice, c->stream));
+  GCHK(c, hipStreamSynchronize(c->stream));  // sg leaves scope
+  hipLaunchKernelGGL(k_pgo_add_keyframes, dim3((n + kThreads - 1) / kThreads), dim3(kThreads), 0, c->stream, n, k0, d_pose,
+                     d_index, p->added[p->added_cur], p->added[p->added_cur ^ 1], p->n, p->e, p->x[p->cur], p->from, p->to,
+                     p->meas, p->sigma, p->robust, p->odom_sigma);
+  GCHK(c, hipGetLastError());
+  p->added_cur ^= 1;
+  for (int k = k0; k < n; k++) {
+    p->h_from.push_back(p->n + k - 1);
+    p->h_to.push_back(p->n + k);
+  }
+  p->n += n;
+  p->e += n_edges;
+  p->adj_dirty = true;
+  return LISLAM_OK;
+}
+
+int check_index(lislam_ctx* c, const char* who, const char* name, const int32_t* index, int n, int bound) {
+  for (int k = 0; k < n; k++) {
+    if (index[k] < 0 || index[k] >= bound)
+      return gfail(c, LISLAM_ERR_ARG, "%s: %s[%d] = %d outside [0, %d)", who, name, k, index[k], bound);
+    if (k > 0 && index[k] <= index[k - 1])
+      return gfail(c, LISLAM_ERR_ARG, "%s: %s[%d] = %d after %d: the list must be strictly increasing", who, name, k, index[k],
+                   index[k - 1]);
+  }
+  return LISLAM_OK;
+}
+
+}  // namespace
+
+int lislam_pgo_add_keyframes(lislam_pgo* p, const double* pose7, int32_t n_poses, const int32_t* index, int32_t n,
+                             const double* var6) {
+  if (!p || n < 0 || n_poses < 0 || (n > 0 && (!pose7 || !index))) return LISLAM_ERR_ARG;
+  lislam_ctx* c = p->ctx;
+  if (var6 && !positive(var6, 6)) return gfail(c, LISLAM_ERR_ARG, "lislam_pgo_add_keyframes: variances must be positive");
+  int rc;
+  if ((rc = check_index(c, "lislam_pgo_add_keyframes", "index", index, n, n_poses))) return rc;
+  if (n == 0) return LISLAM_OK;
+  return add_keyframes(p, "lislam_pgo_add_keyframes", nullptr, pose7, n_poses, index, n, var6);
+}
+
+int lislam_pgo_add_batch_scans(lislam_pgo* p, lislam_batch* b, const int32_t* scans, int32_t n, const double* var6) {
+  if (!p || !b || n < 0 || (n > 0 && !scans)) return LISLAM_ERR_ARG;
+  lislam_ctx* c = p->ctx;
+  if (b->ctx != c) return gfail(c, LISLAM_ERR_ARG, "lislam_pgo_add_batch_scans: the batch belongs to another context");
+  if (var6 && !positive(var6, 6)) return gfail(c, LISLAM_ERR_ARG, "lislam_pgo_add_batch_scans: variances must be positive");
+  if (n > 0 && b->extracted < 1)
+    return gfail(c, LISLAM_ERR_STATE, "lislam_pgo_add_batch_scans: extract the batch and run its odometry first");
+  int rc;
+  if ((rc = check_index(c, "lislam_pgo_add_batch_scans", "scans", scans, n, b->extracted))) return rc;
+  if (n == 0) return LISLAM_OK;
+  if ((rc = lislam_batch_settle(b)) != LISLAM_OK) return rc;
+  return add_keyframes(p, "lislam_pgo_add_batch_scans", b->oa.pose, nullptr, b->extracted, scans, n, var6);
 }
 
 int lislam_pgo_linearize(lislam_pgo* p, double* residual, double* J_from, double* J_to, double* weight, double* cost) {

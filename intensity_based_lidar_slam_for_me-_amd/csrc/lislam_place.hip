@@ -529,6 +529,38 @@ int lislam_place_add_batch(lislam_place* p, lislam_batch* b, int32_t first_scan,
   return describe(p, cl, n_scans);
 }
 
+int lislam_place_add_batch_scans(lislam_place* p, lislam_batch* b, const int32_t* scans, int32_t n) {
+  if (!p || !b || n < 0 || (n > 0 && !scans)) return LISLAM_ERR_ARG;
+  lislam_ctx* c = p->ctx;
+  if (b->ctx != c) return pfail(c, LISLAM_ERR_ARG, "lislam_place_add_batch_scans: the batch belongs to another context");
+  if (!b->fa.track) return pfail(c, LISLAM_ERR_STATE, "lislam_place_add_batch_scans: cloud_track not materialized (want_images=0)");
+  if (n > 0 && b->extracted < 1) return pfail(c, LISLAM_ERR_STATE, "lislam_place_add_batch_scans: extract the batch first");
+  for (int k = 0; k < n; k++)
+    if (scans[k] < 0 || scans[k] >= b->extracted)
+      return pfail(c, LISLAM_ERR_ARG, "lislam_place_add_batch_scans: scans[%d] = %d outside [0, %d)", k, scans[k], b->extracted);
+  if ((int64_t)p->n + n > p->capacity)
+    return pfail(c, LISLAM_ERR_CAPACITY, "lislam_place_add_batch_scans: %d + %d entries exceed the capacity %d", p->n, n,
+                 p->capacity);
+  if (n == 0) return LISLAM_OK;
+  hipSetDevice(c->device);
+  int rc;
+  if ((rc = reserve(c, &p->meta, &p->meta_bytes, (size_t)n * (sizeof(long long) + sizeof(int))))) return rc;
+  // cloud k = scan scans[k]: the packed form's (offset, count) pairs over the batch's cloud_track
+  std::vector<long long> off(n);
+  std::vector<int> cnt(n, b->N);
+  for (int k = 0; k < n; k++) off[k] = (long long)scans[k] * b->N;
+  long long* d_off = static_cast<long long*>(p->meta);
+  int* d_cnt = reinterpret_cast<int*>(d_off + n);
+  // pageable sources: these copies have read them when they return
+  PCHK(c, hipMemcpyAsync(d_off, off.data(), (size_t)n * sizeof(long long), hipMemcpyHostToDevice, c->stream));
+  PCHK(c, hipMemcpyAsync(d_cnt, cnt.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  Clouds cl{reinterpret_cast<const float4*>(b->fa.track), d_off, d_cnt, 0, blocks_for(b->N)};
+  if ((rc = describe(p, cl, n))) return rc;
+  // the host arrays above leave scope: the copies that read them must have run
+  PCHK(c, hipStreamSynchronize(c->stream));
+  return LISLAM_OK;
+}
+
 int lislam_place_detect(lislam_place* p, int32_t first, int32_t n, int32_t* loop_id, float* yaw, double* min_dist,
                         int32_t* nn_idx, int32_t* nn_align) {
   if (!p || n < 0) return LISLAM_ERR_ARG;

@@ -90,6 +90,13 @@ class KeyframePool:
         nat.check(self.ctx.lib.lislam_keyframes_add_batch(self.h, batch.h, int(first), int(n)), self.ctx.h,
                   "lislam_keyframes_add_batch")
 
+    def add_batch_scans(self, batch, scans) -> None:
+        """cloud_track of the listed scans of an extracted batch (any order, repeats allowed), one gather
+        launch: what ``add_batch(batch, s, 1)`` for every s in ``scans`` would leave."""
+        s = np.ascontiguousarray(np.atleast_1d(scans), np.int32).reshape(-1)
+        nat.check(self.ctx.lib.lislam_keyframes_add_batch_scans(self.h, batch.h, nat.ptr(s) if s.size else None, s.shape[0]),
+                  self.ctx.h, "lislam_keyframes_add_batch_scans")
+
     def cloud(self, i: int) -> np.ndarray:
         """Keyframe i as (n, 4) float32."""
         n = ctypes.c_int32()
@@ -131,6 +138,87 @@ class KeyframePool:
                                                   pT, nat.ptr(T_icp), nat.ptr(T_c2m), nat.ptr(fit), nat.ptr(info)),
                   self.ctx.h, "lislam_loop_verify")
         return T_icp, T_c2m, fit, info
+
+
+class KeyframeSelector:
+    """``feature_tracker::getKeyframe`` (``src/intensity_feature_tracker.cpp:741-815``) behind tfBroadcast's
+    ``T_s2m = T_s2m * T_s2s`` (``:819``), its state on the device (``lislam_keysel_*``).  The reference's
+    first branch (``cloudKeyPoses3D_->points.empty()``, filled by another thread) is taken exactly once
+    here, by the first good frame.  Each step returns ``(keyframe_id (n,) int32 with -1 = not a keyframe,
+    T_s2m (n, 4, 4), nodes (n_selected, 26))``; a node row is time, id, cur_position[3], prev_position[3],
+    cur_rotation[9], prev_rotation[9] (``FactorGraphNode``, ``src/keyframe.h:115-121``)."""
+
+    def __init__(self, ctx, time_interval: float = 0.3, distance_interval: float = 0.3):
+        self.ctx = ctx
+        self.cfg = nat.KeyselConfig(float(time_interval), float(distance_interval))
+        h = ctypes.c_void_p()
+        nat.check(ctx.lib.lislam_keysel_create(ctx.h, ctypes.byref(self.cfg), ctypes.byref(h)), ctx.h, "lislam_keysel_create")
+        self.h = h
+
+    def close(self):
+        if self.h:
+            if self.ctx.h:
+                self.ctx.lib.lislam_keysel_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def _out(n):
+        return np.full(n, -1, np.int32), ctypes.c_int32(), np.zeros((n, 4, 4)), np.zeros((n, 26))
+
+    def step(self, T_s2s, good, times):
+        """n frames in stream order: ``T_s2s`` (n, 7) q x,y,z,w, t and ``good`` (n,) int32, each a numpy array
+        or a contiguous torch device tensor (float64 / int32); ``times`` (n,) on the host."""
+        t = np.ascontiguousarray(times, np.float64).reshape(-1)
+        n = t.shape[0]
+        if hasattr(T_s2s, "data_ptr"):
+            if str(T_s2s.dtype) != "torch.float64" or not T_s2s.is_contiguous() or T_s2s.numel() != 7 * n:
+                raise ValueError("T_s2s must be a contiguous float64 tensor of (n, 7)")
+            kT, pT = T_s2s, ctypes.c_void_p(T_s2s.data_ptr())
+        else:
+            kT = np.ascontiguousarray(T_s2s, np.float64).reshape(-1, 7)
+            if kT.shape[0] != n:
+                raise ValueError("T_s2s must hold one row per time")
+            pT = nat.ptr(kT)
+        if hasattr(good, "data_ptr"):
+            if str(good.dtype) != "torch.int32" or not good.is_contiguous() or good.numel() != n:
+                raise ValueError("good must be a contiguous int32 tensor of (n,)")
+            kg, pg = good, ctypes.c_void_p(good.data_ptr())
+        else:
+            kg = np.ascontiguousarray(good, np.int32).reshape(-1)
+            if kg.shape[0] != n:
+                raise ValueError("good must hold one flag per time")
+            pg = nat.ptr(kg)
+        ids, nsel, T, node = self._out(n)
+        nat.check(self.ctx.lib.lislam_keysel_step(self.h, pT if n else None, pg if n else None, nat.ptr(t) if n else None, n,
+                                                  nat.ptr(ids), ctypes.byref(nsel), nat.ptr(T), nat.ptr(node)), self.ctx.h,
+                  "lislam_keysel_step")
+        return ids, T, node[:nsel.value].copy()
+
+    def step_batch(self, batch, first: int, n: int, times):
+        """The same for scans [first, first + n) of a batch whose intensity_odometry has run: the OUT_ORB_T rows
+        and OUT_ORB_STATS[0] == 1 are read on the device."""
+        t = np.ascontiguousarray(times, np.float64).reshape(-1)
+        if t.shape[0] != int(n):
+            raise ValueError("times must hold one entry per scan")
+        m = max(int(n), 0)
+        ids, nsel, T, node = self._out(m)
+        nat.check(self.ctx.lib.lislam_keysel_step_batch(self.h, batch.h, int(first), int(n), nat.ptr(t) if m else None,
+                                                        nat.ptr(ids), ctypes.byref(nsel), nat.ptr(T), nat.ptr(node)), self.ctx.h,
+                  "lislam_keysel_step_batch")
+        return ids, T, node[:nsel.value].copy()
+
+    def state(self):
+        """(keyframes selected so far, T_s2m (4, 4), the last keyframe's time: NaN before the first)."""
+        n, T, t = ctypes.c_int32(), np.zeros((4, 4)), np.zeros(1)
+        nat.check(self.ctx.lib.lislam_keysel_state(self.h, ctypes.byref(n), nat.ptr(T), nat.ptr(t)), self.ctx.h,
+                  "lislam_keysel_state")
+        return n.value, T, float(t[0])
 
 
 def close_loops(pool: KeyframePool, pose_graph, cur_ids, loop_ids, cfg: IcpConfig | None = None, robust: bool = False):

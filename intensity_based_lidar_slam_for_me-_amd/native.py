@@ -1,4 +1,4 @@
-"""ctypes binding of ``liblislam.so`` (the C ABI declared in ``include/lislam.h``).
+"""ctypes binding of ``liblislam.so`` (the C ABI declared in ``include/lislam.h`` and ``include/lislam_feeds.h``).
 
 The HIP library is the only compute path: if it is missing this module raises, it never falls
 back to a CPU implementation.
@@ -59,7 +59,11 @@ EXPORTED_SYMBOLS = (
     "lislam_mapwin_create", "lislam_mapwin_destroy", "lislam_mapwin_size", "lislam_mapwin_push", "lislam_mapwin_keyframe",
     "lislam_mapwin_match", "lislam_mapwin_records", "lislam_mapopt_step_window", "lislam_orb_detect_map",
     "lislam_batch_mapopt_window",
+    "lislam_keysel_create", "lislam_keysel_destroy", "lislam_keysel_step", "lislam_keysel_step_batch", "lislam_keysel_state",
 )
+# include/lislam_feeds.h: the feeds for a list of scans
+FEED_SYMBOLS = ("lislam_keyframes_add_batch_scans", "lislam_place_add_batch_scans", "lislam_bow_add_batch_scans",
+                "lislam_pgo_add_keyframes", "lislam_pgo_add_batch_scans")
 
 MAP_KERNELS = ("k_knn", "k_fit", "k_lm_eval", "k_lm_step", "map_rebuild", "map_downsample", "k_orb_pyramid",
                "k_orb_fast", "k_orb_select", "k_orb_finish", "k_orb_blur", "k_orb_desc", "k_orb_match", "k_orb_lm",
@@ -70,14 +74,15 @@ MATCH_LINE, MATCH_PLANE = 0, 1
 PLACE_DESC, PLACE_RING_KEY, PLACE_SECTOR_KEY = 0, 1, 2
 PLACE_KERNELS = ("k_sc_describe", "k_sc_finish", "k_sc_detect", "k_sc_distance")
 BOW_WORDS, BOW_VALUES = 0, 1
-BOW_KERNELS = ("k_bow_words", "k_bow_vector", "k_bow_query", "k_bow_select", "k_bow_score", "k_bow_gather")
+BOW_KERNELS = ("k_bow_words", "k_bow_vector", "k_bow_query", "k_bow_select", "k_bow_score", "k_bow_gather", "k_bow_scan_list")
 BOW_TRAIN_MAX_L, BOW_TRAIN_MAX_DESCRIPTORS = 10, 1 << 23
 BOW_PHASES = ("seed", "assign", "means", "partition")
 BOW_TRAIN_KERNELS = ("k_bowt_ingest", "k_bowt_locate", "k_bowt_seed", "k_bowt_assign", "k_bowt_means", "k_bowt_majority",
                      "k_bowt_tilecount", "k_bowt_offsets", "k_bowt_scatter", "k_bowt_ni")
 PGO_CONVERGED, PGO_LAMBDA_LIMIT, PGO_MAX_ITERATIONS = 0, 1, 2
 PGO_KERNELS = ("k_pgo_linearize", "k_pgo_assemble", "k_pgo_sum", "k_pgo_factor", "k_pgo_cg", "k_pgo_retract",
-               "k_pgo_add_batch", "k_pgo_pose6d")
+               "k_pgo_add_batch", "k_pgo_pose6d", "k_pgo_add_keyframes")
+KEYSEL_KERNELS = ("k_keysel", "k_kf_gather")  # the selector and the keyframe pool's list feed
 
 
 class Config(ctypes.Structure):
@@ -177,6 +182,15 @@ class PgoConfig(ctypes.Structure):
 
     def __init__(self, max_iterations=50, cg_max_iterations=0, lambda_init=1e-4, rel_cost_tol=1e-10, cg_rel_tol=1e-12):
         super().__init__(max_iterations, cg_max_iterations, lambda_init, rel_cost_tol, cg_rel_tol)
+
+
+class KeyselConfig(ctypes.Structure):
+    """lislam_keysel_config: getKeyframe's two gates; defaults = config/spot.yaml:35-36."""
+
+    _fields_ = [("time_interval", ctypes.c_double), ("distance_interval", ctypes.c_double)]
+
+    def __init__(self, time_interval=0.3, distance_interval=0.3):
+        super().__init__(time_interval, distance_interval)
 
 
 class Frame(ctypes.Structure):
@@ -333,9 +347,19 @@ def load(path: str = LIB_PATH):
     L.lislam_mapopt_step_window.argtypes = [vp, vp, vp, vp, _i32, vp, _i32, vp, vp, _i32, vp, vp, vp, vp]
     L.lislam_orb_detect_map.argtypes = [vp, vp, vp, vp, _i32, _i32, _i32, vp, vp, vp, _i32, _i32p]
     L.lislam_batch_mapopt_window.argtypes = [vp, vp, vp, vp, _i32, _i32, vp, vp, vp, vp, vp]
+    L.lislam_keysel_create.argtypes = [vp, ctypes.POINTER(KeyselConfig), ctypes.POINTER(vp)]
+    L.lislam_keysel_destroy.argtypes = [vp]
+    L.lislam_keysel_step.argtypes = [vp, vp, vp, vp, _i32, vp, _i32p, vp, vp]
+    L.lislam_keysel_step_batch.argtypes = [vp, vp, _i32, _i32, vp, vp, _i32p, vp, vp]
+    L.lislam_keysel_state.argtypes = [vp, _i32p, vp, vp]
+    L.lislam_keyframes_add_batch_scans.argtypes = [vp, vp, vp, _i32]
+    L.lislam_place_add_batch_scans.argtypes = [vp, vp, vp, _i32]
+    L.lislam_bow_add_batch_scans.argtypes = [vp, vp, vp, _i32]
+    L.lislam_pgo_add_keyframes.argtypes = [vp, vp, _i32, vp, _i32, vp]
+    L.lislam_pgo_add_batch_scans.argtypes = [vp, vp, vp, _i32, vp]
     L.lislam_map_set_timing.argtypes = [vp, _i32]
     L.lislam_map_kernel_times.argtypes = [vp, _fp, _i32p]
-    for name in EXPORTED_SYMBOLS:
+    for name in EXPORTED_SYMBOLS + FEED_SYMBOLS:
         getattr(L, name).restype = getattr(L, name).restype or ctypes.c_int
     L.lislam_last_error.restype = ctypes.c_char_p
     _LIB = L

@@ -71,6 +71,13 @@ class ScanContext:
         nat.check(self.ctx.lib.lislam_place_add_batch(self.h, batch.h, int(first), int(n)), self.ctx.h,
                   "lislam_place_add_batch")
 
+    def add_batch_scans(self, batch, scans) -> None:
+        """The listed scans of an extracted batch (any order, repeats allowed) in one set of launches: what
+        ``add_batch(batch, s, 1)`` for every s in ``scans`` would leave."""
+        s = np.ascontiguousarray(np.atleast_1d(scans), np.int32).reshape(-1)
+        nat.check(self.ctx.lib.lislam_place_add_batch_scans(self.h, batch.h, nat.ptr(s) if s.size else None, s.shape[0]),
+                  self.ctx.h, "lislam_place_add_batch_scans")
+
     def detect(self, first: int | None = None, n: int | None = None) -> Detection:
         """detectLoopClosureID as it returned when keyframe k was the newest, k in [first, first + n)
         (default: every keyframe)."""

@@ -157,6 +157,32 @@ class PoseGraph:
         nat.check(self.ctx.lib.lislam_pgo_add_batch(self.h, batch.h, int(first), int(n), None if v is None else nat.ptr(v)),
                   self.ctx.h, "lislam_pgo_add_batch")
 
+    def add_keyframes(self, poses, index, variances=None) -> None:
+        """mapOdomHandle (:395-514) for the keyframes ``index`` (strictly increasing) of one trajectory
+        ``poses`` (n_poses, 7), a numpy array or a float64 torch device tensor: node k = poses[index[k]], edge
+        (k - 1, k) = poses[index[k-1]]^-1 poses[index[k]].  On a graph that is not empty the first keyframe gets
+        an edge from the last node, measured from the pose that node was added with."""
+        idx = np.ascontiguousarray(np.atleast_1d(index), np.int32).reshape(-1)
+        v = None if variances is None else np.ascontiguousarray(variances, np.float64).reshape(6)
+        if hasattr(poses, "data_ptr"):
+            if str(poses.dtype) != "torch.float64" or not poses.is_contiguous() or poses.numel() % 7:
+                raise ValueError("poses must be a contiguous float64 tensor of (n_poses, 7)")
+            keep, n_poses, pp = poses, poses.numel() // 7, ctypes.c_void_p(poses.data_ptr())
+        else:
+            keep = np.ascontiguousarray(poses, np.float64).reshape(-1, 7)
+            n_poses, pp = keep.shape[0], nat.ptr(keep)
+        nat.check(self.ctx.lib.lislam_pgo_add_keyframes(self.h, pp if n_poses else None, n_poses,
+                                                        nat.ptr(idx) if idx.size else None, idx.shape[0],
+                                                        None if v is None else nat.ptr(v)), self.ctx.h, "lislam_pgo_add_keyframes")
+
+    def add_batch_scans(self, batch, scans, variances=None) -> None:
+        """``add_keyframes`` with poses = the batch's OUT_POSE rows, read on the device.  OUT_POSE starts again
+        at the identity with every batch: a stream over several batches goes through ``add_keyframes``."""
+        s = np.ascontiguousarray(np.atleast_1d(scans), np.int32).reshape(-1)
+        v = None if variances is None else np.ascontiguousarray(variances, np.float64).reshape(6)
+        nat.check(self.ctx.lib.lislam_pgo_add_batch_scans(self.h, batch.h, nat.ptr(s) if s.size else None, s.shape[0],
+                                                          None if v is None else nat.ptr(v)), self.ctx.h, "lislam_pgo_add_batch_scans")
+
     def edges(self, first: int = 0, n: int | None = None):
         """(from, to, meas (n, 7), variances (n, 6), robust) of edges [first, first + n)."""
         n = self.size()[1] - first if n is None else int(n)
