@@ -14,6 +14,7 @@
 #include "../../include/lislam.h"
 #include "lislam_batch.hpp"
 #include "lislam_ctx.hpp"
+#include "lislam_host.hpp"
 #include "lislam_internal.hpp"
 #include "lislam_mapwin.hpp"
 
@@ -21,24 +22,6 @@ using namespace lislam;
 
 
 namespace {
-
-int fail(lislam_ctx* c, int code, const char* fmt, ...) {
-  if (c) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    c->err = buf;
-  }
-  return code;
-}
-
-#define HIPCHK(ctx, x)                                                                  \
-  do {                                                                                  \
-    hipError_t e_ = (x);                                                                \
-    if (e_ != hipSuccess) return fail(ctx, LISLAM_ERR_DEVICE, "%s: %s", #x, hipGetErrorString(e_)); \
-  } while (0)
 
 template <typename T>
 int dalloc(lislam_batch* b, T** p, size_t count) {
@@ -155,9 +138,9 @@ static int round_streams(lislam_batch* b) {
   for (int g = 1; g < lislam_batch::kGroups; g++) {
     if (!b->odo_stream[g] && !(b->odo_stream[g] = lislam::round_stream(c->device, g)))
       return fail(c, LISLAM_ERR_DEVICE, "stream");
-    if (!b->odo_join[g]) HIPCHK(c, hipEventCreateWithFlags(&b->odo_join[g], hipEventDisableTiming));
+    if (!b->odo_join[g]) LISLAM_HIPCHK(c, hipEventCreateWithFlags(&b->odo_join[g], hipEventDisableTiming));
   }
-  if (lislam_batch::kGroups > 1 && !b->odo_fork) HIPCHK(c, hipEventCreateWithFlags(&b->odo_fork, hipEventDisableTiming));
+  if (lislam_batch::kGroups > 1 && !b->odo_fork) LISLAM_HIPCHK(c, hipEventCreateWithFlags(&b->odo_fork, hipEventDisableTiming));
   return LISLAM_OK;
 }
 
@@ -168,7 +151,7 @@ int lislam_synchronize(lislam_ctx* c) {
     const int rc = engine_settle(b);
     if (rc != LISLAM_OK) return rc;
   }
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  LISLAM_HIPCHK(c, hipStreamSynchronize(c->stream));
   return LISLAM_OK;
 }
 
@@ -194,13 +177,13 @@ static int engine_settle(lislam_batch* b) {
   hipSetDevice(c->device);
   if (b->eng_pending) {
     lislam::wait_engine_launched(&b->eng_req);  // the dispatcher has recorded the join events
-    HIPCHK(c, hipStreamWaitEvent(c->stream, b->eng_join_r, 0));
-    HIPCHK(c, hipStreamWaitEvent(c->stream, b->eng_join_i, 0));
+    LISLAM_HIPCHK(c, hipStreamWaitEvent(c->stream, b->eng_join_r, 0));
+    LISLAM_HIPCHK(c, hipStreamWaitEvent(c->stream, b->eng_join_i, 0));
     b->eng_pending = false;
   }
   if (!b->eng_check) return LISLAM_OK;
   // the host waits for the engine itself (not the context stream, which may hold later work)
-  HIPCHK(c, hipEventSynchronize(b->eng_done));
+  LISLAM_HIPCHK(c, hipEventSynchronize(b->eng_done));
   // h_abort: the engine's error word (which wait gave up) and its sticky abort word
   if (b->h_abort[1] == 0) {
     b->eng_check = false;
@@ -208,12 +191,12 @@ static int engine_settle(lislam_batch* b) {
   }
   // eng_check stays set until the re-run is queued: a failure below leaves the recovery to the
   // batch's next call instead of losing it
-  HIPCHK(c, hipMemsetAsync(b->oa.eng_ctl + 3, 0, sizeof(unsigned), c->stream));
+  LISLAM_HIPCHK(c, hipMemsetAsync(b->oa.eng_ctl + 3, 0, sizeof(unsigned), c->stream));
   // the per-round schedule has no device waits: it cannot abort
   if (round_streams(b) != LISLAM_OK) return LISLAM_ERR_DEVICE;
   lislam::launch_odometry(b->eng_args, b->odo_stream, lislam_batch::kGroups, b->odo_fork, b->odo_join, nullptr,
                           &lislam_batch::event_cb, b);
-  HIPCHK(c, hipGetLastError());
+  LISLAM_HIPCHK(c, hipGetLastError());
   b->eng_abort_code = b->h_abort[0];
   b->h_abort[0] = b->h_abort[1] = 0;
   b->eng_fallbacks++;
@@ -393,8 +376,8 @@ int lislam_batch_upload(lislam_batch* b, const void* points, int32_t n_scans, co
   hipSetDevice(c->device);
   const size_t n = (size_t)n_scans * b->N;
   if (is_packed(layout)) {
-    HIPCHK(c, hipMemcpyAsync((void*)b->fa.pts, points, n * 16, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    LISLAM_HIPCHK(c, hipMemcpyAsync((void*)b->fa.pts, points, n * 16, hipMemcpyHostToDevice, c->stream));
+    LISLAM_HIPCHK(c, hipStreamSynchronize(c->stream));
   } else {  // the message bytes go to the device scan by scan, the fields are parsed there
     if (layout->point_step < 4 || std::max({layout->off_x, layout->off_y, layout->off_z, layout->off_intensity}) + 4 > layout->point_step)
       return fail(c, LISLAM_ERR_ARG, "bad point layout");
@@ -402,13 +385,13 @@ int lislam_batch_upload(lislam_batch* b, const void* points, int32_t n_scans, co
     if ((rc_wire(b, scan_bytes)) != LISLAM_OK) return fail(c, LISLAM_ERR_DEVICE, "staging allocation failed");
     const lislam::WireLayout L{layout->point_step, layout->off_x, layout->off_y, layout->off_z, layout->off_intensity};
     for (int s = 0; s < n_scans; s++) {
-      HIPCHK(c, hipMemcpyAsync(b->wire, static_cast<const uint8_t*>(points) + s * scan_bytes, scan_bytes, hipMemcpyDefault,
-                               c->stream));
+      LISLAM_HIPCHK(c, hipMemcpyAsync(b->wire, static_cast<const uint8_t*>(points) + s * scan_bytes, scan_bytes, hipMemcpyDefault,
+                                      c->stream));
       lislam::launch_unpack_layout(static_cast<const uint8_t*>(b->wire), b->N, L,
                                    const_cast<lislam::P4*>(b->fa.pts) + (size_t)s * b->N, c->stream);
     }
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    LISLAM_HIPCHK(c, hipGetLastError());
+    LISLAM_HIPCHK(c, hipStreamSynchronize(c->stream));
   }
   return LISLAM_OK;
 }
@@ -427,8 +410,8 @@ int lislam_batch_upload_async(lislam_batch* b, const void* points, int32_t n_sca
   const size_t need = (size_t)b->max_scans * scan_bytes;
   if (b->ring_bytes < need) {
     // a new staging area: everything queued on either stream may still use the old one
-    if (b->copy_stream) HIPCHK(c, hipStreamSynchronize(b->copy_stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (b->copy_stream) LISLAM_HIPCHK(c, hipStreamSynchronize(b->copy_stream));
+    LISLAM_HIPCHK(c, hipStreamSynchronize(c->stream));
     if (b->ring) hipFree(b->ring);
     b->ring = nullptr;
     b->ring_bytes = 0;
@@ -436,13 +419,13 @@ int lislam_batch_upload_async(lislam_batch* b, const void* points, int32_t n_sca
     b->ring_bytes = need;
     std::fill(b->chunk_used.begin(), b->chunk_used.end(), 0);
   }
-  if (!b->copy_stream) HIPCHK(c, hipStreamCreateWithFlags(&b->copy_stream, hipStreamNonBlocking));
+  if (!b->copy_stream) LISLAM_HIPCHK(c, hipStreamCreateWithFlags(&b->copy_stream, hipStreamNonBlocking));
   constexpr int kChunk = 16;
   const int nchunks = (n_scans + kChunk - 1) / kChunk;
   while ((int)b->chunk_landed.size() < nchunks) {
     hipEvent_t e1 = nullptr, e2 = nullptr;
-    HIPCHK(c, hipEventCreateWithFlags(&e1, hipEventDisableTiming));
-    HIPCHK(c, hipEventCreateWithFlags(&e2, hipEventDisableTiming));
+    LISLAM_HIPCHK(c, hipEventCreateWithFlags(&e1, hipEventDisableTiming));
+    LISLAM_HIPCHK(c, hipEventCreateWithFlags(&e2, hipEventDisableTiming));
     b->chunk_landed.push_back(e1);
     b->chunk_parsed.push_back(e2);
     b->chunk_used.push_back(0);
@@ -452,16 +435,16 @@ int lislam_batch_upload_async(lislam_batch* b, const void* points, int32_t n_sca
     const int s0 = k * kChunk, ns = std::min(kChunk, n_scans - s0);
     uint8_t* dst = static_cast<uint8_t*>(b->ring) + (size_t)s0 * scan_bytes;
     // the chunk's staging bytes are free once the previous upload's parse of them has run
-    if (b->chunk_used[k]) HIPCHK(c, hipStreamWaitEvent(b->copy_stream, b->chunk_parsed[k], 0));
-    HIPCHK(c, hipMemcpyAsync(dst, static_cast<const uint8_t*>(points) + (size_t)s0 * scan_bytes, (size_t)ns * scan_bytes,
-                             hipMemcpyHostToDevice, b->copy_stream));
-    HIPCHK(c, hipEventRecord(b->chunk_landed[k], b->copy_stream));
-    HIPCHK(c, hipStreamWaitEvent(c->stream, b->chunk_landed[k], 0));
+    if (b->chunk_used[k]) LISLAM_HIPCHK(c, hipStreamWaitEvent(b->copy_stream, b->chunk_parsed[k], 0));
+    LISLAM_HIPCHK(c, hipMemcpyAsync(dst, static_cast<const uint8_t*>(points) + (size_t)s0 * scan_bytes, (size_t)ns * scan_bytes,
+                                    hipMemcpyHostToDevice, b->copy_stream));
+    LISLAM_HIPCHK(c, hipEventRecord(b->chunk_landed[k], b->copy_stream));
+    LISLAM_HIPCHK(c, hipStreamWaitEvent(c->stream, b->chunk_landed[k], 0));
     lislam::launch_unpack_layout(dst, ns * b->N, L, const_cast<lislam::P4*>(b->fa.pts) + (size_t)s0 * b->N, c->stream);
-    HIPCHK(c, hipEventRecord(b->chunk_parsed[k], c->stream));
+    LISLAM_HIPCHK(c, hipEventRecord(b->chunk_parsed[k], c->stream));
     b->chunk_used[k] = 1;
   }
-  HIPCHK(c, hipGetLastError());
+  LISLAM_HIPCHK(c, hipGetLastError());
   return LISLAM_OK;
 }
 
@@ -494,11 +477,11 @@ int lislam_batch_mapopt_corner(lislam_batch* b, lislam_map* m, lislam_map* cm, i
   const size_t bytes = (size_t)(ng + nlf + nls) * 16;
   if ((rc = rc_wire(b, std::max<size_t>(bytes, 16)))) return fail(c, rc, "lislam_batch_mapopt: staging allocation");
   uint8_t* dst = static_cast<uint8_t*>(b->wire);
-  if (ng) HIPCHK(c, hipMemcpyAsync(dst, g, (size_t)ng * 16, hipMemcpyDeviceToDevice, c->stream));
-  if (nlf) HIPCHK(c, hipMemcpyAsync(dst + (size_t)ng * 16, lf, (size_t)nlf * 16, hipMemcpyDeviceToDevice, c->stream));
+  if (ng) LISLAM_HIPCHK(c, hipMemcpyAsync(dst, g, (size_t)ng * 16, hipMemcpyDeviceToDevice, c->stream));
+  if (nlf) LISLAM_HIPCHK(c, hipMemcpyAsync(dst + (size_t)ng * 16, lf, (size_t)nlf * 16, hipMemcpyDeviceToDevice, c->stream));
   if (nls)
-    HIPCHK(c, hipMemcpyAsync(dst + (size_t)(ng + nlf) * 16, ls, (size_t)nls * 16, hipMemcpyDeviceToDevice, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+    LISLAM_HIPCHK(c, hipMemcpyAsync(dst + (size_t)(ng + nlf) * 16, ls, (size_t)nls * 16, hipMemcpyDeviceToDevice, c->stream));
+  LISLAM_HIPCHK(c, hipStreamSynchronize(c->stream));
   return lislam_mapopt_step_corner(m, cm, reinterpret_cast<const float*>(dst), ng + nlf,
                                    reinterpret_cast<const float*>(dst + (size_t)(ng + nlf) * 16), nls, odom, state,
                                    out_pose, summary);
@@ -541,11 +524,11 @@ int lislam_batch_mapopt_window(lislam_batch* b, lislam_map* m, lislam_map* cm, l
   const size_t bytes = (size_t)(ng + nlf + nls) * 16;
   if ((rc = rc_wire(b, std::max<size_t>(bytes, 16)))) return fail(c, rc, "lislam_batch_mapopt_window: staging allocation");
   uint8_t* dst = static_cast<uint8_t*>(b->wire);
-  if (ng) HIPCHK(c, hipMemcpyAsync(dst, g, (size_t)ng * 16, hipMemcpyDeviceToDevice, c->stream));
-  if (nlf) HIPCHK(c, hipMemcpyAsync(dst + (size_t)ng * 16, lf, (size_t)nlf * 16, hipMemcpyDeviceToDevice, c->stream));
+  if (ng) LISLAM_HIPCHK(c, hipMemcpyAsync(dst, g, (size_t)ng * 16, hipMemcpyDeviceToDevice, c->stream));
+  if (nlf) LISLAM_HIPCHK(c, hipMemcpyAsync(dst + (size_t)ng * 16, lf, (size_t)nlf * 16, hipMemcpyDeviceToDevice, c->stream));
   if (nls)
-    HIPCHK(c, hipMemcpyAsync(dst + (size_t)(ng + nlf) * 16, ls, (size_t)nls * 16, hipMemcpyDeviceToDevice, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+    LISLAM_HIPCHK(c, hipMemcpyAsync(dst + (size_t)(ng + nlf) * 16, ls, (size_t)nls * 16, hipMemcpyDeviceToDevice, c->stream));
+  LISLAM_HIPCHK(c, hipStreamSynchronize(c->stream));
   return lislam_mapopt_step_window(m, cm, win, reinterpret_cast<const float*>(dst), ng + nlf,
                                    reinterpret_cast<const float*>(dst + (size_t)(ng + nlf) * 16), nls, ddesc, dp3d, nf,
                                    odom, state, out_pose, summary);
@@ -576,9 +559,9 @@ int lislam_batch_download_cloud(lislam_batch* b, int32_t what, int32_t scan, voi
   if (rc_wire(b, bytes) != LISLAM_OK) return fail(c, LISLAM_ERR_DEVICE, "staging allocation failed");
   const lislam::WireLayout L{layout->point_step, layout->off_x, layout->off_y, layout->off_z, layout->off_intensity};
   lislam::launch_pack_layout(static_cast<const lislam::P4*>(src), cnt, L, static_cast<uint8_t*>(b->wire), c->stream);
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipMemcpyAsync(dst, b->wire, bytes, hipMemcpyDefault, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  LISLAM_HIPCHK(c, hipGetLastError());
+  LISLAM_HIPCHK(c, hipMemcpyAsync(dst, b->wire, bytes, hipMemcpyDefault, c->stream));
+  LISLAM_HIPCHK(c, hipStreamSynchronize(c->stream));
   return LISLAM_OK;
 }
 
@@ -618,9 +601,9 @@ int lislam_batch_extract(lislam_batch* b, int32_t n_scans) {
   }
   launch_features(f, c->stream, ev, b->ev_images);
   launch_target_index(b->oa, n_scans, c->stream);  // spatial index of the clouds odometry searches
-  if (ev) HIPCHK(c, hipEventRecord(ev[4], c->stream));
-  HIPCHK(c, hipEventRecord(b->eng_ready, c->stream));  // the chain engine's inputs
-  HIPCHK(c, hipGetLastError());
+  if (ev) LISLAM_HIPCHK(c, hipEventRecord(ev[4], c->stream));
+  LISLAM_HIPCHK(c, hipEventRecord(b->eng_ready, c->stream));  // the chain engine's inputs
+  LISLAM_HIPCHK(c, hipGetLastError());
   b->extracted = n_scans;
   return LISLAM_OK;
 }
@@ -678,10 +661,10 @@ static int run_odometry(lislam_batch* b, int n_scans, int chain_len, const doubl
     // the caller's arrays -> pinned staging -> device, so they may be freed on return
     const size_t init_bytes = sizeof(double) * 14 * (size_t)b->max_scans;
     if (!b->h_stage) {
-      HIPCHK(c, hipHostMalloc(&b->h_stage, init_bytes + sizeof(int) * (size_t)b->max_scans, hipHostMallocDefault));
-      HIPCHK(c, hipEventCreateWithFlags(&b->stage_ev, hipEventDisableTiming));
+      LISLAM_HIPCHK(c, hipHostMalloc(&b->h_stage, init_bytes + sizeof(int) * (size_t)b->max_scans, hipHostMallocDefault));
+      LISLAM_HIPCHK(c, hipEventCreateWithFlags(&b->stage_ev, hipEventDisableTiming));
     }
-    if (b->stage_busy) HIPCHK(c, hipEventSynchronize(b->stage_ev));  // the previous upload has been read
+    if (b->stage_busy) LISLAM_HIPCHK(c, hipEventSynchronize(b->stage_ev));  // the previous upload has been read
     double* hi = static_cast<double*>(b->h_stage);
     int* hg = reinterpret_cast<int*>(static_cast<char*>(b->h_stage) + init_bytes);
     if (use_aloam) {
@@ -689,19 +672,19 @@ static int run_odometry(lislam_batch* b, int n_scans, int chain_len, const doubl
       const bool on_device = hipPointerGetAttributes(&attr, use_aloam) == hipSuccess && attr.type == hipMemoryTypeDevice;
       (void)hipGetLastError();  // an unregistered host pointer reports an error here
       if (on_device) {
-        HIPCHK(c, hipMemcpyAsync(b->d_gate, use_aloam, sizeof(int) * n_scans, hipMemcpyDeviceToDevice, c->stream));
+        LISLAM_HIPCHK(c, hipMemcpyAsync(b->d_gate, use_aloam, sizeof(int) * n_scans, hipMemcpyDeviceToDevice, c->stream));
       } else {
         std::memcpy(hg, use_aloam, sizeof(int) * n_scans);
-        HIPCHK(c, hipMemcpyAsync(b->d_gate, hg, sizeof(int) * n_scans, hipMemcpyHostToDevice, c->stream));
+        LISLAM_HIPCHK(c, hipMemcpyAsync(b->d_gate, hg, sizeof(int) * n_scans, hipMemcpyHostToDevice, c->stream));
       }
       o.gate = b->d_gate;
     }
     if (init_host) {
       std::memcpy(hi, init_host, sizeof(double) * 14 * o.n_chains);
-      HIPCHK(c, hipMemcpyAsync(b->d_init, hi, sizeof(double) * 14 * o.n_chains, hipMemcpyHostToDevice, c->stream));
+      LISLAM_HIPCHK(c, hipMemcpyAsync(b->d_init, hi, sizeof(double) * 14 * o.n_chains, hipMemcpyHostToDevice, c->stream));
       o.init_state = b->d_init;
     }
-    HIPCHK(c, hipEventRecord(b->stage_ev, c->stream));
+    LISLAM_HIPCHK(c, hipEventRecord(b->stage_ev, c->stream));
     b->stage_busy = true;
   }
   const int G = lislam_batch::kGroups;
@@ -724,12 +707,12 @@ static int run_odometry(lislam_batch* b, int n_scans, int chain_len, const doubl
       const bool single = getenv("LISLAM_ENGINE_SINGLE") && atoi(getenv("LISLAM_ENGINE_SINGLE")) == 1;
       b->eng_split = !single && lislam::engine_streams_available(c->device) ? 1 : 0;
       if (b->eng_split) {
-        HIPCHK(c, hipEventCreateWithFlags(&b->eng_fork, hipEventDisableTiming));
-        HIPCHK(c, hipEventCreateWithFlags(&b->eng_join_r, hipEventDisableTiming));
-        HIPCHK(c, hipEventCreateWithFlags(&b->eng_join_i, hipEventDisableTiming));
+        LISLAM_HIPCHK(c, hipEventCreateWithFlags(&b->eng_fork, hipEventDisableTiming));
+        LISLAM_HIPCHK(c, hipEventCreateWithFlags(&b->eng_join_r, hipEventDisableTiming));
+        LISLAM_HIPCHK(c, hipEventCreateWithFlags(&b->eng_join_i, hipEventDisableTiming));
       }
-      HIPCHK(c, hipEventCreateWithFlags(&b->eng_done, hipEventDisableTiming));
-      HIPCHK(c, hipHostMalloc((void**)&b->h_abort, 2 * sizeof(unsigned), hipHostMallocDefault));
+      LISLAM_HIPCHK(c, hipEventCreateWithFlags(&b->eng_done, hipEventDisableTiming));
+      LISLAM_HIPCHK(c, hipHostMalloc((void**)&b->h_abort, 2 * sizeof(unsigned), hipHostMallocDefault));
       b->h_abort[0] = b->h_abort[1] = 0;
     }
     if (ev) { e0 = b->get_event(); e1 = b->get_event(); }
@@ -738,7 +721,7 @@ static int run_odometry(lislam_batch* b, int n_scans, int chain_len, const doubl
       // the inputs: everything queued on the context stream so far (the last extract, any per-round
       // odometry queued after it, the staging copies just queued); the launch copies its abort words
       // to h_abort and records eng_done on its own stream
-      HIPCHK(c, hipEventRecord(b->eng_ready, c->stream));
+      LISLAM_HIPCHK(c, hipEventRecord(b->eng_ready, c->stream));
       if (o.eng_depth > 1 && lislam::engine_dispatch_enabled()) {
         // to the device's dispatcher: launched on the first free engine slot once the inputs exist.
         // Depth 1 keeps the direct gate: one engine at a time has no slot to choose, and the host
@@ -764,17 +747,17 @@ static int run_odometry(lislam_batch* b, int n_scans, int chain_len, const doubl
       else b->eng_split = 0;  // no engine streams on this device after all: the single launch below
     }
     if (!queued) {
-      if (ev) HIPCHK(c, hipEventRecord(e0, c->stream));
+      if (ev) LISLAM_HIPCHK(c, hipEventRecord(e0, c->stream));
       lislam::launch_odometry_chain(o, c->stream);
-      if (ev) HIPCHK(c, hipEventRecord(e1, c->stream));
-      HIPCHK(c, hipMemcpyAsync(b->h_abort, b->oa.eng_ctl + 2, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
-      HIPCHK(c, hipEventRecord(b->eng_done, c->stream));
+      if (ev) LISLAM_HIPCHK(c, hipEventRecord(e1, c->stream));
+      LISLAM_HIPCHK(c, hipMemcpyAsync(b->h_abort, b->oa.eng_ctl + 2, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+      LISLAM_HIPCHK(c, hipEventRecord(b->eng_done, c->stream));
     }
     b->eng_args = o;
     b->eng_check = true;
     b->engine_ran = true;
     if (ev) ev->push_back({6, e0, e1});
-    HIPCHK(c, hipGetLastError());
+    LISLAM_HIPCHK(c, hipGetLastError());
     return LISLAM_OK;
   }
   b->engine_ran = false;
@@ -783,7 +766,7 @@ static int run_odometry(lislam_batch* b, int n_scans, int chain_len, const doubl
     lislam::launch_to_end_identity(o, b->deskew, 0, c->stream);
   launch_odometry(o, b->odo_stream, G, b->odo_fork, b->odo_join, ev, &lislam_batch::event_cb, b,
                   mode != LISLAM_DISTORTION_OFF ? &b->deskew : nullptr);
-  HIPCHK(c, hipGetLastError());
+  LISLAM_HIPCHK(c, hipGetLastError());
   if (mode == LISLAM_DISTORTION_TO_END) {
     b->te_scans = n_scans;
     b->te_full = !node;
@@ -847,7 +830,7 @@ int lislam_batch_kernel_times(lislam_batch* b, float* ms_per_call, int32_t* laun
   SETTLE(b);
   lislam_ctx* c = b->ctx;
   hipSetDevice(c->device);
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  LISLAM_HIPCHK(c, hipStreamSynchronize(c->stream));
   double acc[LISLAM_NUM_KERNELS] = {0};
   int launches[LISLAM_NUM_KERNELS] = {0};
   auto el = [&](hipEvent_t a0, hipEvent_t a1) -> double {
@@ -887,7 +870,7 @@ int lislam_batch_kernel_times(lislam_batch* b, float* ms_per_call, int32_t* laun
 static int output_source(lislam_batch* b, int what, int scan, const void** src_out, int* cnt_out, size_t* esz_out) {
   lislam_ctx* c = b->ctx;
   hipSetDevice(c->device);
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  LISLAM_HIPCHK(c, hipStreamSynchronize(c->stream));
   const size_t N = b->N;
   const FeatureArgs& f = b->fa;
   const OdomArgs& o = b->oa;
@@ -895,7 +878,7 @@ static int output_source(lislam_batch* b, int what, int scan, const void** src_o
   const void* src = nullptr;
   size_t esz = 0;
   auto devint = [&](const int* p, int* v) -> int {
-    HIPCHK(c, hipMemcpy(v, p, sizeof(int), hipMemcpyDeviceToHost));
+    LISLAM_HIPCHK(c, hipMemcpy(v, p, sizeof(int), hipMemcpyDeviceToHost));
     return LISLAM_OK;
   };
   int ncloud = 0;
@@ -994,7 +977,7 @@ int lislam_batch_download(lislam_batch* b, int32_t what, int32_t scan, void* dst
   if (n) *n = cnt;
   if (!dst) return LISLAM_OK;  // count only
   if (cnt > cap) return fail(c, LISLAM_ERR_CAPACITY, "output %d needs %d elements, cap %d", what, cnt, cap);
-  if (cnt > 0) HIPCHK(c, hipMemcpy(dst, src, (size_t)cnt * esz, hipMemcpyDeviceToHost));
+  if (cnt > 0) LISLAM_HIPCHK(c, hipMemcpy(dst, src, (size_t)cnt * esz, hipMemcpyDeviceToHost));
   return LISLAM_OK;
 }
 
@@ -1015,10 +998,10 @@ int lislam_scan_registration(lislam_ctx* c, const void* points, const lislam_poi
   // every output of the scan in one pass: the counts once, then the copies, one wait at the end
   const FeatureArgs& f = b->fa;
   const int N = b->N;
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  LISLAM_HIPCHK(c, hipStreamSynchronize(c->stream));
   int ncloud = 0, nfeat[4] = {0, 0, 0, 0};
-  HIPCHK(c, hipMemcpy(&ncloud, f.n_cloud, sizeof(int), hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy(nfeat, f.n_feat, sizeof(nfeat), hipMemcpyDeviceToHost));
+  LISLAM_HIPCHK(c, hipMemcpy(&ncloud, f.n_cloud, sizeof(int), hipMemcpyDeviceToHost));
+  LISLAM_HIPCHK(c, hipMemcpy(nfeat, f.n_feat, sizeof(nfeat), hipMemcpyDeviceToHost));
   struct Item { const void* src; int cnt; size_t esz; void* dst; int cap; int* n; const char* name; };
   const Item items[] = {
       {f.cloud, ncloud, 16, out->laser_cloud, out->cap_laser_cloud, &out->n_laser_cloud, "laser_cloud"},
@@ -1034,9 +1017,9 @@ int lislam_scan_registration(lislam_ctx* c, const void* points, const lislam_poi
     if (!it.src) return fail(c, LISLAM_ERR_STATE, "%s unavailable (context created without images)", it.name);
     if (it.cnt > it.cap) return fail(c, LISLAM_ERR_CAPACITY, "%s needs %d elements, cap %d", it.name, it.cnt, it.cap);
     if (it.n) *it.n = it.cnt;
-    if (it.cnt > 0) HIPCHK(c, hipMemcpyAsync(it.dst, it.src, (size_t)it.cnt * it.esz, hipMemcpyDeviceToHost, c->stream));
+    if (it.cnt > 0) LISLAM_HIPCHK(c, hipMemcpyAsync(it.dst, it.src, (size_t)it.cnt * it.esz, hipMemcpyDeviceToHost, c->stream));
   }
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  LISLAM_HIPCHK(c, hipStreamSynchronize(c->stream));
   return LISLAM_OK;
 }
 
@@ -1082,7 +1065,7 @@ static int put_frame(lislam_batch* b, int slot, const lislam_frame* fr) {
     return fail(c, LISLAM_ERR_CAPACITY, "frame exceeds feature capacities");
   const FeatureArgs& f = b->fa;
   auto cp = [&](P4* dst, const float* src, int n) -> int {
-    if (n > 0) HIPCHK(c, hipMemcpyAsync(dst, src, (size_t)n * 16, hipMemcpyHostToDevice, c->stream));
+    if (n > 0) LISLAM_HIPCHK(c, hipMemcpyAsync(dst, src, (size_t)n * 16, hipMemcpyHostToDevice, c->stream));
     return LISLAM_OK;
   };
   int rc = 0;
@@ -1091,7 +1074,7 @@ static int put_frame(lislam_batch* b, int slot, const lislam_frame* fr) {
   rc |= cp(f.flat + (size_t)slot * b->cap_flat, fr->flat, fr->n_flat);
   rc |= cp(f.less_flat + (size_t)slot * b->N, fr->less_flat, fr->n_less_flat);
   const int cnt[4] = {fr->n_sharp, fr->n_less_sharp, fr->n_flat, fr->n_less_flat};
-  HIPCHK(c, hipMemcpyAsync(f.n_feat + slot * 4, cnt, sizeof(cnt), hipMemcpyHostToDevice, c->stream));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(f.n_feat + slot * 4, cnt, sizeof(cnt), hipMemcpyHostToDevice, c->stream));
   // per-line offsets of less_sharp / less_flat (first index whose int(intensity) >= line); they
   // only seed the 1-NN bound, so any non-decreasing array within [0, n] keeps results exact
   const int H = b->H;
@@ -1105,8 +1088,8 @@ static int put_frame(lislam_batch* b, int slot, const lislam_frame* fr) {
       loff[w * (H + 1) + l] = j;
     }
   }
-  HIPCHK(c, hipMemcpyAsync(f.feat_loff + (size_t)slot * 2 * (H + 1), loff.data(), loff.size() * sizeof(int),
-                           hipMemcpyHostToDevice, c->stream));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(f.feat_loff + (size_t)slot * 2 * (H + 1), loff.data(), loff.size() * sizeof(int),
+                                  hipMemcpyHostToDevice, c->stream));
   OdomArgs o = b->oa;
   o.less_sharp = f.less_sharp + (size_t)slot * b->cap_less_sharp;
   o.less_flat = f.less_flat + (size_t)slot * b->N;
@@ -1124,8 +1107,8 @@ static int put_frame(lislam_batch* b, int slot, const lislam_frame* fr) {
     ti->keys += (size_t)slot * 2 * ti->cap;
   }
   launch_target_index(o, 1, c->stream);
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipStreamSynchronize(c->stream));
+  LISLAM_HIPCHK(c, hipGetLastError());
+  LISLAM_HIPCHK(c, hipStreamSynchronize(c->stream));
   return rc ? LISLAM_ERR_DEVICE : LISLAM_OK;
 }
 
@@ -1137,8 +1120,8 @@ static int copy_slot(lislam_batch* b, int from, int to) {
   const hipStream_t st = c->stream;
   auto cp = [&](const void* base, size_t per_slot) -> int {
     const char* p = static_cast<const char*>(base);
-    HIPCHK(c, hipMemcpyAsync(const_cast<char*>(p) + (size_t)to * per_slot, p + (size_t)from * per_slot, per_slot,
-                             hipMemcpyDeviceToDevice, st));
+    LISLAM_HIPCHK(c, hipMemcpyAsync(const_cast<char*>(p) + (size_t)to * per_slot, p + (size_t)from * per_slot, per_slot,
+                                    hipMemcpyDeviceToDevice, st));
     return LISLAM_OK;
   };
   const FeatureArgs& f = b->fa;
@@ -1183,7 +1166,7 @@ static int node_to_end_identity(lislam_batch* b, int slot) {
   OdomArgs o = b->oa;
   o.S = 2;
   lislam::launch_to_end_identity(o, b->deskew, slot, c->stream);
-  HIPCHK(c, hipGetLastError());
+  LISLAM_HIPCHK(c, hipGetLastError());
   return LISLAM_OK;
 }
 
@@ -1219,9 +1202,9 @@ static int odom_step(lislam_odom* od, const lislam_frame* fr, int use_aloam, dou
       size_t esz = 0;
       if ((rc = output_source(b, o.what, 1, &src, &cnt, &esz))) return rc;
       if (cnt > o.cap) return fail(c, LISLAM_ERR_CAPACITY, "output %d needs %d elements", o.what, cnt);
-      if (cnt > 0) HIPCHK(c, hipMemcpyAsync(o.dst, src, (size_t)cnt * esz, hipMemcpyDeviceToHost, c->stream));
+      if (cnt > 0) LISLAM_HIPCHK(c, hipMemcpyAsync(o.dst, src, (size_t)cnt * esz, hipMemcpyDeviceToHost, c->stream));
     }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    LISLAM_HIPCHK(c, hipStreamSynchronize(c->stream));
     // the current frame becomes the last frame (laserOdometry.cpp:793-808), on the device
     if ((rc = copy_slot(b, 1, 0))) return rc;
   }

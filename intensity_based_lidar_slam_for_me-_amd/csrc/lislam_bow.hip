@@ -39,6 +39,7 @@
 #include "lislam_batch.hpp"
 #include "lislam_ctx.hpp"
 #include "lislam_device.hpp"
+#include "lislam_host.hpp"
 
 namespace lislam {
 namespace bow {
@@ -397,6 +398,7 @@ __global__ __launch_bounds__(kThreads) void k_bow_gather(Store st, int e, int* _
 }  // namespace lislam
 
 using namespace lislam::bow;
+using namespace lislam;
 
 struct lislam_bow {
   lislam_ctx* ctx = nullptr;
@@ -409,52 +411,13 @@ struct lislam_bow {
   void* tree_desc = nullptr;
   void* tree_weight = nullptr;
   // grow-only staging: packed descriptors, their words, per-image (offset, count), results
-  void* stage = nullptr;
-  size_t stage_bytes = 0;
-  void* wstage = nullptr;
-  size_t wstage_bytes = 0;
-  void* meta = nullptr;
-  size_t meta_bytes = 0;
-  void* res = nullptr;
-  size_t res_bytes = 0;
+  DBuf stage, wstage, meta, res;
 };
 
 namespace {
 
-int bfail(lislam_ctx* c, int code, const char* fmt, ...) {
-  if (c) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    c->err = buf;
-  }
-  return code;
-}
-
-#define BCHK(ctx, x)                                                                                  \
-  do {                                                                                                \
-    hipError_t e_ = (x);                                                                              \
-    if (e_ != hipSuccess) return bfail(ctx, LISLAM_ERR_DEVICE, "%s: %s", #x, hipGetErrorString(e_)); \
-  } while (0)
-
-int reserve(lislam_ctx* c, void** p, size_t* have, size_t want) {
-  if (want <= *have) return LISLAM_OK;
-  if (*p) {
-    BCHK(c, hipStreamSynchronize(c->stream));
-    (void)hipFree(*p);
-    *p = nullptr;
-    *have = 0;
-  }
-  BCHK(c, hipMalloc(p, want));
-  *have = want;
-  return LISLAM_OK;
-}
-
 void free_bow(lislam_bow* p) {
-  for (void* q : {p->tree_nodes, p->tree_desc, p->tree_weight, (void*)p->st.words, (void*)p->st.vals, (void*)p->st.len, p->stage,
-                  p->wstage, p->meta, p->res})
+  for (void* q : {p->tree_nodes, p->tree_desc, p->tree_weight, (void*)p->st.words, (void*)p->st.vals, (void*)p->st.len})
     if (q) (void)hipFree(q);
   delete p;
 }
@@ -474,13 +437,12 @@ void launch_words(lislam_bow* p, const Source& src, int* words, double* weights)
 // words + vector of the images of src into entries [p->n, p->n + src.n_images)
 int add_images(lislam_bow* p, const Source& src) {
   lislam_ctx* c = p->ctx;
-  int rc;
-  if ((rc = reserve(c, &p->wstage, &p->wstage_bytes, (size_t)src.n_images * src.per_image * sizeof(int)))) return rc;
-  int* words = static_cast<int*>(p->wstage);
+  LISLAM_HIPCHK(c, p->wstage.reserve((size_t)src.n_images * src.per_image * sizeof(int), c->stream));
+  int* words = p->wstage.as<int>();
   launch_words(p, src, words, nullptr);
   hipLaunchKernelGGL(k_bow_vector, dim3(src.n_images), dim3(kThreads), vector_lds(p->F), c->stream, p->T, src, words, p->st,
                      p->n, pow2_at_least(p->F));
-  BCHK(c, hipGetLastError());
+  LISLAM_HIPCHK(c, hipGetLastError());
   p->n += src.n_images;
   return LISLAM_OK;
 }
@@ -496,27 +458,27 @@ int lislam_bow_create(lislam_ctx* c, int32_t n_nodes, const int32_t* parent, con
   lislam_bow_config d = {0.0155, 0.015, 50, 4, 5, 6};  // detectLoop's constants (loop_closure_handler.cpp:127-188)
   if (cfg) d = *cfg;
   if (!parent || !descriptor || !weight || n_nodes < 2 || n_nodes > (1 << 28))
-    return bfail(c, LISLAM_ERR_ARG, "lislam_bow_create: a vocabulary needs its three arrays and at least two nodes");
+    return fail(c, LISLAM_ERR_ARG, "lislam_bow_create: a vocabulary needs its three arrays and at least two nodes");
   if (capacity < 1 || max_features < 1 || max_features > kMaxFeat || (int64_t)capacity * max_features > (1ll << 31) - 1)
-    return bfail(c, LISLAM_ERR_ARG, "lislam_bow_create: capacity >= 1, max_features 1..%d, capacity * max_features < 2^31", kMaxFeat);
+    return fail(c, LISLAM_ERR_ARG, "lislam_bow_create: capacity >= 1, max_features 1..%d, capacity * max_features < 2^31", kMaxFeat);
   if (d.max_results < 1 || d.max_results > kMaxResults || d.min_loop_search_gap < 0 || !std::isfinite(d.min_loop_bow_threshold) ||
       !std::isfinite(d.index_score_threshold))
-    return bfail(c, LISLAM_ERR_ARG, "lislam_bow_create: max_results 1..%d, min_loop_search_gap >= 0, finite thresholds", kMaxResults);
+    return fail(c, LISLAM_ERR_ARG, "lislam_bow_create: max_results 1..%d, min_loop_search_gap >= 0, finite thresholds", kMaxResults);
   // the tree: parents before children, <= 64 children per node, finite weights >= 0
-  if (parent[0] != -1) return bfail(c, LISLAM_ERR_ARG, "lislam_bow_create: parent[0] = %d, the root's must be -1", parent[0]);
+  if (parent[0] != -1) return fail(c, LISLAM_ERR_ARG, "lislam_bow_create: parent[0] = %d, the root's must be -1", parent[0]);
   std::vector<int> nchild(n_nodes, 0);
   for (int i = 1; i < n_nodes; i++) {
     if (parent[i] < 0 || parent[i] >= i)
-      return bfail(c, LISLAM_ERR_ARG, "lislam_bow_create: parent[%d] = %d, want 0 <= parent < %d", i, parent[i], i);
+      return fail(c, LISLAM_ERR_ARG, "lislam_bow_create: parent[%d] = %d, want 0 <= parent < %d", i, parent[i], i);
     nchild[parent[i]]++;
   }
   int max_children = 0;
   for (int i = 0; i < n_nodes; i++) {
     if (nchild[i] > kMaxChildren)
-      return bfail(c, LISLAM_ERR_ARG, "lislam_bow_create: node %d has %d children, at most %d", i, nchild[i], kMaxChildren);
+      return fail(c, LISLAM_ERR_ARG, "lislam_bow_create: node %d has %d children, at most %d", i, nchild[i], kMaxChildren);
     max_children = std::max(max_children, nchild[i]);
     if (!std::isfinite(weight[i]) || weight[i] < 0)
-      return bfail(c, LISLAM_ERR_ARG, "lislam_bow_create: weight[%d] = %g, want a finite weight >= 0", i, weight[i]);
+      return fail(c, LISLAM_ERR_ARG, "lislam_bow_create: weight[%d] = %g, want a finite weight >= 0", i, weight[i]);
   }
   // children lists in ascending id (a counting sort by parent keeps the order)
   std::vector<int> cstart(n_nodes + 1, 0);
@@ -582,7 +544,7 @@ int lislam_bow_create(lislam_ctx* c, int32_t n_nodes, const int32_t* parent, con
   if (!ok) {
     (void)hipGetLastError();
     free_bow(p);
-    return bfail(c, LISLAM_ERR_DEVICE, "lislam_bow_create: device allocation failed");
+    return fail(c, LISLAM_ERR_DEVICE, "lislam_bow_create: device allocation failed");
   }
   p->st.capacity = capacity;
   p->T = Tree{static_cast<const int2*>(p->tree_nodes), static_cast<const uint4*>(p->tree_desc),
@@ -612,25 +574,24 @@ static int stage_packed(lislam_bow* p, const char* who, const void* desc, const 
   int max_count = 0;
   for (int k = 0; k < n_images; k++) {
     if (counts[k] < 0 || counts[k] > p->F)
-      return bfail(c, LISLAM_ERR_ARG, "%s: counts[%d] = %d, want 0..max_features (%d)", who, k, counts[k], p->F);
+      return fail(c, LISLAM_ERR_ARG, "%s: counts[%d] = %d, want 0..max_features (%d)", who, k, counts[k], p->F);
     total += counts[k];
     max_count = std::max(max_count, counts[k]);
   }
-  if (total > 0 && !desc) return bfail(c, LISLAM_ERR_ARG, "%s: null descriptors", who);
+  if (total > 0 && !desc) return fail(c, LISLAM_ERR_ARG, "%s: null descriptors", who);
   hipSetDevice(c->device);
-  int rc;
-  if ((rc = reserve(c, &p->stage, &p->stage_bytes, (size_t)std::max<int64_t>(total, 1) * 32))) return rc;
-  if ((rc = reserve(c, &p->meta, &p->meta_bytes, (size_t)n_images * (sizeof(long long) + sizeof(int))))) return rc;
+  LISLAM_HIPCHK(c, p->stage.reserve((size_t)std::max<int64_t>(total, 1) * 32, c->stream));
+  LISLAM_HIPCHK(c, p->meta.reserve((size_t)n_images * (sizeof(long long) + sizeof(int)), c->stream));
   std::vector<long long> off(n_images);
   long long run = 0;
   for (int k = 0; k < n_images; k++) { off[k] = run; run += counts[k]; }
-  long long* d_off = static_cast<long long*>(p->meta);
+  long long* d_off = p->meta.as<long long>();
   int* d_cnt = reinterpret_cast<int*>(d_off + n_images);
   // pageable sources: these copies have read them when they return
-  BCHK(c, hipMemcpyAsync(d_off, off.data(), (size_t)n_images * sizeof(long long), hipMemcpyHostToDevice, c->stream));
-  BCHK(c, hipMemcpyAsync(d_cnt, counts, (size_t)n_images * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  if (total) BCHK(c, hipMemcpyAsync(p->stage, desc, (size_t)total * 32, hipMemcpyDefault, c->stream));
-  *src = Source{static_cast<const uint4*>(p->stage), d_off, d_cnt, 0, n_images, std::max(max_count, 1), p->F};
+  LISLAM_HIPCHK(c, hipMemcpyAsync(d_off, off.data(), (size_t)n_images * sizeof(long long), hipMemcpyHostToDevice, c->stream));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(d_cnt, counts, (size_t)n_images * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  if (total) LISLAM_HIPCHK(c, hipMemcpyAsync(p->stage.p, desc, (size_t)total * 32, hipMemcpyDefault, c->stream));
+  *src = Source{p->stage.as<const uint4>(), d_off, d_cnt, 0, n_images, std::max(max_count, 1), p->F};
   return LISLAM_OK;
 }
 
@@ -639,75 +600,60 @@ int lislam_bow_add(lislam_bow* p, const void* desc, const int32_t* counts, int32
   lislam_ctx* c = p->ctx;
   if (n_images == 0) return LISLAM_OK;
   if ((int64_t)p->n + n_images > p->capacity)
-    return bfail(c, LISLAM_ERR_CAPACITY, "lislam_bow_add: %d + %d entries exceed the capacity %d", p->n, n_images, p->capacity);
+    return fail(c, LISLAM_ERR_CAPACITY, "lislam_bow_add: %d + %d entries exceed the capacity %d", p->n, n_images, p->capacity);
   Source src{};
   int rc;
   if ((rc = stage_packed(p, "lislam_bow_add", desc, counts, n_images, &src))) return rc;
   if ((rc = add_images(p, src))) return rc;
-  BCHK(c, hipStreamSynchronize(c->stream));
+  LISLAM_HIPCHK(c, hipStreamSynchronize(c->stream));
   return LISLAM_OK;
 }
 
 int lislam_bow_add_batch(lislam_bow* p, lislam_batch* b, int32_t first_scan, int32_t n_scans) {
   if (!p || !b) return LISLAM_ERR_ARG;
   lislam_ctx* c = p->ctx;
-  if (b->ctx != c) return bfail(c, LISLAM_ERR_ARG, "lislam_bow_add_batch: the batch belongs to another context");
-  if (first_scan < 0 || n_scans < 0 || (int64_t)first_scan + n_scans > b->max_scans)
-    return bfail(c, LISLAM_ERR_ARG, "lislam_bow_add_batch: scans [%d, %d + %d) out of range", first_scan, first_scan, n_scans);
-  const uint8_t* desc = nullptr;
-  const int* counts = nullptr;
-  int cap = 0, nfeatures = 0, ran = 0;
-  const int rc = lislam_orb_batch_descriptors(b, &desc, &counts, &cap, &nfeatures, &ran);
-  if (rc == LISLAM_ERR_STATE || (rc == LISLAM_OK && first_scan + n_scans > ran))
-    return bfail(c, LISLAM_ERR_STATE, "lislam_bow_add_batch: run lislam_batch_intensity_odometry over %d scans first",
-                 first_scan + n_scans);
-  if (rc) return rc;
-  if (nfeatures > p->F)
-    return bfail(c, LISLAM_ERR_ARG, "lislam_bow_add_batch: the batch detects %d features, max_features is %d", nfeatures, p->F);
-  if ((int64_t)p->n + n_scans > p->capacity)
-    return bfail(c, LISLAM_ERR_CAPACITY, "lislam_bow_add_batch: %d + %d entries exceed the capacity %d", p->n, n_scans,
-                 p->capacity);
+  const char* who = "lislam_bow_add_batch";
+  LISLAM_RC(check_same_context(c, who, b));
+  LISLAM_RC(check_scan_range(c, who, b, first_scan, n_scans));
+  OrbDescriptors o;
+  LISLAM_RC(orb_descriptors(c, who, b, first_scan + n_scans, &o));
+  if (o.nfeatures > p->F)
+    return fail(c, LISLAM_ERR_ARG, "lislam_bow_add_batch: the batch detects %d features, max_features is %d", o.nfeatures, p->F);
+  LISLAM_RC(check_capacity(c, who, p->n, n_scans, "entries", p->capacity));
   if (n_scans == 0) return LISLAM_OK;
   hipSetDevice(c->device);
   // a scan keeps at most nfeatures keypoints; max_count bounds the rows read whatever the count says
-  Source src{reinterpret_cast<const uint4*>(desc + (size_t)first_scan * cap * 32), nullptr, counts + first_scan, cap, n_scans,
-             std::min(nfeatures, cap), std::min(nfeatures, cap)};
+  Source src{reinterpret_cast<const uint4*>(o.desc + (size_t)first_scan * o.cap * 32), nullptr, o.counts + first_scan, o.cap,
+             n_scans, std::min(o.nfeatures, o.cap), std::min(o.nfeatures, o.cap)};
   return add_images(p, src);
 }
 
 int lislam_bow_add_batch_scans(lislam_bow* p, lislam_batch* b, const int32_t* scans, int32_t n) {
   if (!p || !b || n < 0 || (n > 0 && !scans)) return LISLAM_ERR_ARG;
   lislam_ctx* c = p->ctx;
-  if (b->ctx != c) return bfail(c, LISLAM_ERR_ARG, "lislam_bow_add_batch_scans: the batch belongs to another context");
-  const uint8_t* desc = nullptr;
-  const int* counts = nullptr;
-  int cap = 0, nfeatures = 0, ran = 0;
-  int rc = lislam_orb_batch_descriptors(b, &desc, &counts, &cap, &nfeatures, &ran);
-  if (rc == LISLAM_ERR_STATE)
-    return bfail(c, LISLAM_ERR_STATE, "lislam_bow_add_batch_scans: run lislam_batch_intensity_odometry first");
-  if (rc) return rc;
-  for (int k = 0; k < n; k++)
-    if (scans[k] < 0 || scans[k] >= ran)
-      return bfail(c, LISLAM_ERR_ARG, "lislam_bow_add_batch_scans: scans[%d] = %d outside [0, %d)", k, scans[k], ran);
-  if (nfeatures > p->F)
-    return bfail(c, LISLAM_ERR_ARG, "lislam_bow_add_batch_scans: the batch detects %d features, max_features is %d", nfeatures,
-                 p->F);
-  if ((int64_t)p->n + n > p->capacity)
-    return bfail(c, LISLAM_ERR_CAPACITY, "lislam_bow_add_batch_scans: %d + %d entries exceed the capacity %d", p->n, n,
-                 p->capacity);
+  const char* who = "lislam_bow_add_batch_scans";
+  LISLAM_RC(check_same_context(c, who, b));
+  OrbDescriptors o;
+  LISLAM_RC(orb_descriptors(c, who, b, -1, &o));
+  LISLAM_RC(check_index(c, who, "scans", scans, n, o.ran, false));
+  if (o.nfeatures > p->F)
+    return fail(c, LISLAM_ERR_ARG, "lislam_bow_add_batch_scans: the batch detects %d features, max_features is %d", o.nfeatures,
+                p->F);
+  LISLAM_RC(check_capacity(c, who, p->n, n, "entries", p->capacity));
   if (n == 0) return LISLAM_OK;
   hipSetDevice(c->device);
   // [offsets long long n][counts int n][scans int n]
-  if ((rc = reserve(c, &p->meta, &p->meta_bytes, (size_t)n * (sizeof(long long) + 2 * sizeof(int))))) return rc;
-  long long* d_off = static_cast<long long*>(p->meta);
+  LISLAM_HIPCHK(c, p->meta.reserve((size_t)n * (sizeof(long long) + 2 * sizeof(int)), c->stream));
+  long long* d_off = p->meta.as<long long>();
   int* d_cnt = reinterpret_cast<int*>(d_off + n);
   int* d_scans = d_cnt + n;
   // pageable source: the copy has read it when it returns
-  BCHK(c, hipMemcpyAsync(d_scans, scans, (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  hipLaunchKernelGGL(k_bow_scan_list, dim3((n + kThreads - 1) / kThreads), dim3(kThreads), 0, c->stream, d_scans, n, counts, cap,
-                     d_off, d_cnt);
+  LISLAM_HIPCHK(c, hipMemcpyAsync(d_scans, scans, (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  hipLaunchKernelGGL(k_bow_scan_list, dim3((n + kThreads - 1) / kThreads), dim3(kThreads), 0, c->stream, d_scans, n, o.counts,
+                     o.cap, d_off, d_cnt);
   // as the range form: max_count bounds the rows read whatever the count says
-  Source src{reinterpret_cast<const uint4*>(desc), d_off, d_cnt, 0, n, std::min(nfeatures, cap), std::min(nfeatures, cap)};
+  Source src{reinterpret_cast<const uint4*>(o.desc), d_off, d_cnt, 0, n, std::min(o.nfeatures, o.cap),
+             std::min(o.nfeatures, o.cap)};
   return add_images(p, src);
 }
 
@@ -716,16 +662,15 @@ int lislam_bow_detect(lislam_bow* p, int32_t first, int32_t n, int32_t* loop_id,
   if (!p || n < 0) return LISLAM_ERR_ARG;
   lislam_ctx* c = p->ctx;
   if (first < 0 || (int64_t)first + n > p->n)
-    return bfail(c, LISLAM_ERR_ARG, "lislam_bow_detect: keyframes [%d, %d + %d) out of range (size %d)", first, first, n, p->n);
+    return fail(c, LISLAM_ERR_ARG, "lislam_bow_detect: keyframes [%d, %d + %d) out of range (size %d)", first, first, n, p->n);
   if (n == 0) return LISLAM_OK;
   hipSetDevice(c->device);
   const size_t N = (size_t)n, R = (size_t)p->D.max_results;
   const int stride = std::max(first + n, 1);  // a query sees fewer entries than its own index
   const int chunk = std::min(n, kQueryChunk);
-  int rc;
   // [ret_score double N R][scores double chunk stride][loop_id N][n_ret N][ret_id N R]
-  if ((rc = reserve(c, &p->res, &p->res_bytes, N * R * 8 + (size_t)chunk * stride * 8 + N * 8 + N * R * 4))) return rc;
-  double* d_score = static_cast<double*>(p->res);
+  LISLAM_HIPCHK(c, p->res.reserve(N * R * 8 + (size_t)chunk * stride * 8 + N * 8 + N * R * 4, c->stream));
+  double* d_score = p->res.as<double>();
   double* d_acc = d_score + N * R;
   int* d_loop = reinterpret_cast<int*>(d_acc + (size_t)chunk * stride);
   int* d_nret = d_loop + N;
@@ -738,12 +683,12 @@ int lislam_bow_detect(lislam_bow* p, int32_t first, int32_t n, int32_t* loop_id,
                        stride, p->F);
     hipLaunchKernelGGL(k_bow_select, dim3(m), dim3(kThreads), 0, c->stream, p->D, first + q0, d_acc, stride, q0, o);
   }
-  BCHK(c, hipGetLastError());
-  if (loop_id) BCHK(c, hipMemcpyAsync(loop_id, d_loop, N * 4, hipMemcpyDeviceToHost, c->stream));
-  if (n_ret) BCHK(c, hipMemcpyAsync(n_ret, d_nret, N * 4, hipMemcpyDeviceToHost, c->stream));
-  if (ret_id) BCHK(c, hipMemcpyAsync(ret_id, d_id, N * R * 4, hipMemcpyDeviceToHost, c->stream));
-  if (ret_score) BCHK(c, hipMemcpyAsync(ret_score, d_score, N * R * 8, hipMemcpyDeviceToHost, c->stream));
-  BCHK(c, hipStreamSynchronize(c->stream));
+  LISLAM_HIPCHK(c, hipGetLastError());
+  if (loop_id) LISLAM_HIPCHK(c, hipMemcpyAsync(loop_id, d_loop, N * 4, hipMemcpyDeviceToHost, c->stream));
+  if (n_ret) LISLAM_HIPCHK(c, hipMemcpyAsync(n_ret, d_nret, N * 4, hipMemcpyDeviceToHost, c->stream));
+  if (ret_id) LISLAM_HIPCHK(c, hipMemcpyAsync(ret_id, d_id, N * R * 4, hipMemcpyDeviceToHost, c->stream));
+  if (ret_score) LISLAM_HIPCHK(c, hipMemcpyAsync(ret_score, d_score, N * R * 8, hipMemcpyDeviceToHost, c->stream));
+  LISLAM_HIPCHK(c, hipStreamSynchronize(c->stream));
   return LISLAM_OK;
 }
 
@@ -752,48 +697,46 @@ int lislam_bow_score(lislam_bow* p, const int32_t* a, const int32_t* b, int32_t 
   lislam_ctx* c = p->ctx;
   for (int k = 0; k < n_pairs; k++)
     if (a[k] < 0 || a[k] >= p->n || b[k] < 0 || b[k] >= p->n)
-      return bfail(c, LISLAM_ERR_ARG, "lislam_bow_score: pair %d = (%d, %d) out of range (size %d)", k, a[k], b[k], p->n);
+      return fail(c, LISLAM_ERR_ARG, "lislam_bow_score: pair %d = (%d, %d) out of range (size %d)", k, a[k], b[k], p->n);
   if (n_pairs == 0) return LISLAM_OK;
   hipSetDevice(c->device);
-  int rc;
   const size_t N = (size_t)n_pairs;
-  if ((rc = reserve(c, &p->res, &p->res_bytes, N * 16))) return rc;
-  double* d_score = static_cast<double*>(p->res);
+  LISLAM_HIPCHK(c, p->res.reserve(N * 16, c->stream));
+  double* d_score = p->res.as<double>();
   int* d_a = reinterpret_cast<int*>(d_score + N);
   int* d_b = d_a + N;
-  BCHK(c, hipMemcpyAsync(d_a, a, N * 4, hipMemcpyHostToDevice, c->stream));
-  BCHK(c, hipMemcpyAsync(d_b, b, N * 4, hipMemcpyHostToDevice, c->stream));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(d_a, a, N * 4, hipMemcpyHostToDevice, c->stream));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(d_b, b, N * 4, hipMemcpyHostToDevice, c->stream));
   hipLaunchKernelGGL(k_bow_score, dim3((n_pairs + kThreads - 1) / kThreads), dim3(kThreads), 0, c->stream, p->st, d_a, d_b,
                      n_pairs, d_score);
-  BCHK(c, hipGetLastError());
-  if (score) BCHK(c, hipMemcpyAsync(score, d_score, N * 8, hipMemcpyDeviceToHost, c->stream));
-  BCHK(c, hipStreamSynchronize(c->stream));
+  LISLAM_HIPCHK(c, hipGetLastError());
+  if (score) LISLAM_HIPCHK(c, hipMemcpyAsync(score, d_score, N * 8, hipMemcpyDeviceToHost, c->stream));
+  LISLAM_HIPCHK(c, hipStreamSynchronize(c->stream));
   return LISLAM_OK;
 }
 
 int lislam_bow_transform(lislam_bow* p, const void* desc, int32_t n, int32_t* word_id, double* weight) {
   if (!p || n < 0 || (n > 0 && !desc)) return LISLAM_ERR_ARG;
   lislam_ctx* c = p->ctx;
-  if (n > (1 << 24)) return bfail(c, LISLAM_ERR_CAPACITY, "lislam_bow_transform: at most %d descriptors a call", 1 << 24);
+  if (n > (1 << 24)) return fail(c, LISLAM_ERR_CAPACITY, "lislam_bow_transform: at most %d descriptors a call", 1 << 24);
   if (n == 0) return LISLAM_OK;
   hipSetDevice(c->device);
-  int rc;
   const size_t N = (size_t)n;
-  if ((rc = reserve(c, &p->stage, &p->stage_bytes, N * 32))) return rc;
-  if ((rc = reserve(c, &p->meta, &p->meta_bytes, 16))) return rc;
-  if ((rc = reserve(c, &p->res, &p->res_bytes, N * 12))) return rc;
-  double* d_wt = static_cast<double*>(p->res);
+  LISLAM_HIPCHK(c, p->stage.reserve(N * 32, c->stream));
+  LISLAM_HIPCHK(c, p->meta.reserve(16, c->stream));
+  LISLAM_HIPCHK(c, p->res.reserve(N * 12, c->stream));
+  double* d_wt = p->res.as<double>();
   int* d_word = reinterpret_cast<int*>(d_wt + N);
-  int* d_cnt = static_cast<int*>(p->meta);
+  int* d_cnt = p->meta.as<int>();
   const int cnt = n;
-  BCHK(c, hipMemcpyAsync(d_cnt, &cnt, 4, hipMemcpyHostToDevice, c->stream));
-  BCHK(c, hipMemcpyAsync(p->stage, desc, N * 32, hipMemcpyDefault, c->stream));
-  const Source src{static_cast<const uint4*>(p->stage), nullptr, d_cnt, 0, 1, n, n};
+  LISLAM_HIPCHK(c, hipMemcpyAsync(d_cnt, &cnt, 4, hipMemcpyHostToDevice, c->stream));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(p->stage.p, desc, N * 32, hipMemcpyDefault, c->stream));
+  const Source src{p->stage.as<const uint4>(), nullptr, d_cnt, 0, 1, n, n};
   launch_words(p, src, d_word, d_wt);
-  BCHK(c, hipGetLastError());
-  if (word_id) BCHK(c, hipMemcpyAsync(word_id, d_word, N * 4, hipMemcpyDeviceToHost, c->stream));
-  if (weight) BCHK(c, hipMemcpyAsync(weight, d_wt, N * 8, hipMemcpyDeviceToHost, c->stream));
-  BCHK(c, hipStreamSynchronize(c->stream));
+  LISLAM_HIPCHK(c, hipGetLastError());
+  if (word_id) LISLAM_HIPCHK(c, hipMemcpyAsync(word_id, d_word, N * 4, hipMemcpyDeviceToHost, c->stream));
+  if (weight) LISLAM_HIPCHK(c, hipMemcpyAsync(weight, d_wt, N * 8, hipMemcpyDeviceToHost, c->stream));
+  LISLAM_HIPCHK(c, hipStreamSynchronize(c->stream));
   return LISLAM_OK;
 }
 
@@ -801,25 +744,24 @@ int lislam_bow_download(lislam_bow* p, int32_t what, int32_t index, void* dst, i
   if (!p || !dst || cap < 0) return LISLAM_ERR_ARG;
   lislam_ctx* c = p->ctx;
   if (index < 0 || index >= p->n)
-    return bfail(c, LISLAM_ERR_ARG, "lislam_bow_download: index %d out of range (size %d)", index, p->n);
+    return fail(c, LISLAM_ERR_ARG, "lislam_bow_download: index %d out of range (size %d)", index, p->n);
   if (what != LISLAM_BOW_WORDS && what != LISLAM_BOW_VALUES)
-    return bfail(c, LISLAM_ERR_ARG, "lislam_bow_download: unknown output %d", what);
+    return fail(c, LISLAM_ERR_ARG, "lislam_bow_download: unknown output %d", what);
   hipSetDevice(c->device);
   int cnt = 0;
-  BCHK(c, hipMemcpyAsync(&cnt, p->st.len + index, 4, hipMemcpyDeviceToHost, c->stream));
-  BCHK(c, hipStreamSynchronize(c->stream));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(&cnt, p->st.len + index, 4, hipMemcpyDeviceToHost, c->stream));
+  LISLAM_HIPCHK(c, hipStreamSynchronize(c->stream));
   if (n) *n = cnt;
-  if (cap < cnt) return bfail(c, LISLAM_ERR_CAPACITY, "lislam_bow_download: %d elements, capacity %d", cnt, cap);
+  if (cap < cnt) return fail(c, LISLAM_ERR_CAPACITY, "lislam_bow_download: %d elements, capacity %d", cnt, cap);
   if (cnt == 0) return LISLAM_OK;
-  int rc;
-  if ((rc = reserve(c, &p->res, &p->res_bytes, (size_t)p->F * 12))) return rc;
-  double* d_v = static_cast<double*>(p->res);
+  LISLAM_HIPCHK(c, p->res.reserve((size_t)p->F * 12, c->stream));
+  double* d_v = p->res.as<double>();
   int* d_w = reinterpret_cast<int*>(d_v + p->F);
   hipLaunchKernelGGL(k_bow_gather, dim3((cnt + kThreads - 1) / kThreads), dim3(kThreads), 0, c->stream, p->st, index, d_w, d_v);
-  BCHK(c, hipGetLastError());
-  if (what == LISLAM_BOW_WORDS) BCHK(c, hipMemcpyAsync(dst, d_w, (size_t)cnt * 4, hipMemcpyDeviceToHost, c->stream));
-  else BCHK(c, hipMemcpyAsync(dst, d_v, (size_t)cnt * 8, hipMemcpyDeviceToHost, c->stream));
-  BCHK(c, hipStreamSynchronize(c->stream));
+  LISLAM_HIPCHK(c, hipGetLastError());
+  if (what == LISLAM_BOW_WORDS) LISLAM_HIPCHK(c, hipMemcpyAsync(dst, d_w, (size_t)cnt * 4, hipMemcpyDeviceToHost, c->stream));
+  else LISLAM_HIPCHK(c, hipMemcpyAsync(dst, d_v, (size_t)cnt * 8, hipMemcpyDeviceToHost, c->stream));
+  LISLAM_HIPCHK(c, hipStreamSynchronize(c->stream));
   return LISLAM_OK;
 }
 
@@ -1225,10 +1167,6 @@ __global__ __launch_bounds__(kThreads) void k_bowt_ni(const int* __restrict__ wo
 using namespace lislam::bowt;
 
 namespace {
-struct Buf {
-  void* p = nullptr;
-  size_t bytes = 0;
-};
 struct HostNode {  // level order: the children of a node are consecutive, in slot order
   int parent, first_child = 0, n_child = 0;
   uint8_t desc[32];
@@ -1241,7 +1179,7 @@ struct lislam_bow_trainer {
   std::vector<int> img_off{0};  // [n_images + 1] first descriptor of every image
   void* desc = nullptr;         // [cap_desc][32]
   void* img_of = nullptr;       // [cap_desc] int
-  Buf meta, perm, slot, mind, node_of, lvl, centre, tiles, tcount, childcnt, gcount, scalars, tree, words, bitmap;
+  DBuf meta, perm, slot, mind, node_of, lvl, centre, tiles, tcount, childcnt, gcount, scalars, tree, words, bitmap;
   bool trained = false;
   std::vector<int32_t> parent;
   std::vector<uint8_t> descriptor;
@@ -1250,12 +1188,7 @@ struct lislam_bow_trainer {
 
 namespace {
 
-int treserve(lislam_ctx* c, Buf* b, size_t want) { return reserve(c, &b->p, &b->bytes, std::max<size_t>(want, 16)); }
-
 void free_trainer(lislam_bow_trainer* t) {
-  for (Buf* b : {&t->meta, &t->perm, &t->slot, &t->mind, &t->node_of, &t->lvl, &t->centre, &t->tiles, &t->tcount, &t->childcnt,
-                 &t->gcount, &t->scalars, &t->tree, &t->words, &t->bitmap})
-    if (b->p) (void)hipFree(b->p);
   if (t->desc) (void)hipFree(t->desc);
   if (t->img_of) (void)hipFree(t->img_of);
   delete t;
@@ -1264,11 +1197,11 @@ void free_trainer(lislam_bow_trainer* t) {
 // Room for n_images more images of `total` descriptors?
 int check_room(lislam_bow_trainer* t, const char* who, int n_images, int64_t total) {
   if ((int64_t)t->n_images + n_images > t->cap_images)
-    return bfail(t->ctx, LISLAM_ERR_CAPACITY, "%s: %d + %d images exceed the capacity %d", who, t->n_images, n_images,
-                 t->cap_images);
+    return fail(t->ctx, LISLAM_ERR_CAPACITY, "%s: %d + %d images exceed the capacity %d", who, t->n_images, n_images,
+                t->cap_images);
   if ((int64_t)t->n_desc + total > t->cap_desc)
-    return bfail(t->ctx, LISLAM_ERR_CAPACITY, "%s: %d + %lld descriptors exceed the capacity %d", who, t->n_desc,
-                 (long long)total, t->cap_desc);
+    return fail(t->ctx, LISLAM_ERR_CAPACITY, "%s: %d + %lld descriptors exceed the capacity %d", who, t->n_desc,
+                (long long)total, t->cap_desc);
   return LISLAM_OK;
 }
 
@@ -1279,13 +1212,12 @@ int ingest(lislam_bow_trainer* t, const uint4* src, long long src_stride, const 
   std::vector<int> off(n_images + 1);
   off[0] = t->n_desc;
   for (int k = 0; k < n_images; k++) off[k + 1] = off[k] + counts[k];
-  int rc;
-  if ((rc = treserve(c, &t->meta, (size_t)(n_images + 1) * sizeof(int)))) return rc;
-  BCHK(c, hipMemcpyAsync(t->meta.p, off.data(), (size_t)(n_images + 1) * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  LISLAM_HIPCHK(c, t->meta.reserve((size_t)(n_images + 1) * sizeof(int), c->stream));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(t->meta.p, off.data(), (size_t)(n_images + 1) * sizeof(int), hipMemcpyHostToDevice, c->stream));
   hipLaunchKernelGGL(k_bowt_ingest, dim3(n_images), dim3(kThreads), 0, c->stream, src, src_stride,
                      static_cast<const int*>(t->meta.p), t->n_images, static_cast<uint4*>(t->desc), static_cast<int*>(t->img_of));
-  BCHK(c, hipGetLastError());
-  BCHK(c, hipStreamSynchronize(c->stream));  // off leaves scope; the next call may reuse meta
+  LISLAM_HIPCHK(c, hipGetLastError());
+  LISLAM_HIPCHK(c, hipStreamSynchronize(c->stream));  // off leaves scope; the next call may reuse meta
   for (int k = 0; k < n_images; k++) t->img_off.push_back(off[k + 1]);
   t->n_images += n_images;
   t->n_desc = off[n_images];
@@ -1300,9 +1232,9 @@ int lislam_bow_trainer_create(lislam_ctx* c, int32_t cap_images, int32_t cap_des
   if (!c || !out) return LISLAM_ERR_ARG;
   *out = nullptr;
   if (cap_images < 1 || cap_descriptors < 1)
-    return bfail(c, LISLAM_ERR_ARG, "lislam_bow_trainer_create: cap_images >= 1 and cap_descriptors >= 1");
+    return fail(c, LISLAM_ERR_ARG, "lislam_bow_trainer_create: cap_images >= 1 and cap_descriptors >= 1");
   if (cap_descriptors > LISLAM_BOW_TRAIN_MAX_DESCRIPTORS)
-    return bfail(c, LISLAM_ERR_CAPACITY, "lislam_bow_trainer_create: at most %d descriptors", LISLAM_BOW_TRAIN_MAX_DESCRIPTORS);
+    return fail(c, LISLAM_ERR_CAPACITY, "lislam_bow_trainer_create: at most %d descriptors", LISLAM_BOW_TRAIN_MAX_DESCRIPTORS);
   hipSetDevice(c->device);
   lislam_bow_trainer* t = new lislam_bow_trainer();
   t->ctx = c;
@@ -1312,7 +1244,7 @@ int lislam_bow_trainer_create(lislam_ctx* c, int32_t cap_images, int32_t cap_des
       hipMalloc(&t->img_of, (size_t)cap_descriptors * sizeof(int)) != hipSuccess) {
     (void)hipGetLastError();
     free_trainer(t);
-    return bfail(c, LISLAM_ERR_DEVICE, "lislam_bow_trainer_create: device allocation failed");
+    return fail(c, LISLAM_ERR_DEVICE, "lislam_bow_trainer_create: device allocation failed");
   }
   *out = t;
   return LISLAM_OK;
@@ -1339,48 +1271,40 @@ int lislam_bow_trainer_add(lislam_bow_trainer* t, const void* desc, const int32_
   if (n_images == 0) return LISLAM_OK;
   int64_t total = 0;
   for (int k = 0; k < n_images; k++) {
-    if (counts[k] < 0) return bfail(c, LISLAM_ERR_ARG, "lislam_bow_trainer_add: counts[%d] = %d", k, counts[k]);
+    if (counts[k] < 0) return fail(c, LISLAM_ERR_ARG, "lislam_bow_trainer_add: counts[%d] = %d", k, counts[k]);
     total += counts[k];
   }
-  if (total > 0 && !desc) return bfail(c, LISLAM_ERR_ARG, "lislam_bow_trainer_add: null descriptors");
+  if (total > 0 && !desc) return fail(c, LISLAM_ERR_ARG, "lislam_bow_trainer_add: null descriptors");
   int rc;
   if ((rc = check_room(t, "lislam_bow_trainer_add", n_images, total))) return rc;
   hipSetDevice(c->device);
   if (total)
-    BCHK(c, hipMemcpyAsync(static_cast<uint8_t*>(t->desc) + (size_t)t->n_desc * 32, desc, (size_t)total * 32, hipMemcpyDefault,
-                           c->stream));
+    LISLAM_HIPCHK(c, hipMemcpyAsync(static_cast<uint8_t*>(t->desc) + (size_t)t->n_desc * 32, desc, (size_t)total * 32, hipMemcpyDefault,
+                                    c->stream));
   return ingest(t, nullptr, 0, std::vector<int>(counts, counts + n_images));
 }
 
 int lislam_bow_trainer_add_batch(lislam_bow_trainer* t, lislam_batch* b, int32_t first_scan, int32_t n_scans) {
   if (!t || !b) return LISLAM_ERR_ARG;
   lislam_ctx* c = t->ctx;
-  if (b->ctx != c) return bfail(c, LISLAM_ERR_ARG, "lislam_bow_trainer_add_batch: the batch belongs to another context");
-  if (first_scan < 0 || n_scans < 0 || (int64_t)first_scan + n_scans > b->max_scans)
-    return bfail(c, LISLAM_ERR_ARG, "lislam_bow_trainer_add_batch: scans [%d, %d + %d) out of range", first_scan, first_scan,
-                 n_scans);
-  const uint8_t* desc = nullptr;
-  const int* counts = nullptr;
-  int cap = 0, nfeatures = 0, ran = 0;
-  const int rc0 = lislam_orb_batch_descriptors(b, &desc, &counts, &cap, &nfeatures, &ran);
-  if (rc0 == LISLAM_ERR_STATE || (rc0 == LISLAM_OK && first_scan + n_scans > ran))
-    return bfail(c, LISLAM_ERR_STATE, "lislam_bow_trainer_add_batch: run lislam_batch_intensity_odometry over %d scans first",
-                 first_scan + n_scans);
-  if (rc0) return rc0;
+  const char* who = "lislam_bow_trainer_add_batch";
+  LISLAM_RC(check_same_context(c, who, b));
+  LISLAM_RC(check_scan_range(c, who, b, first_scan, n_scans));
+  OrbDescriptors o;
+  LISLAM_RC(orb_descriptors(c, who, b, first_scan + n_scans, &o));
   if (n_scans == 0) return LISLAM_OK;
   hipSetDevice(c->device);
   // the counts decide how much room the scans take: read them (a scan keeps at most nfeatures rows)
   std::vector<int> cnt(n_scans);
-  BCHK(c, hipMemcpyAsync(cnt.data(), counts + first_scan, (size_t)n_scans * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-  BCHK(c, hipStreamSynchronize(c->stream));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(cnt.data(), o.counts + first_scan, (size_t)n_scans * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  LISLAM_HIPCHK(c, hipStreamSynchronize(c->stream));
   int64_t total = 0;
   for (int& v : cnt) {
-    v = std::max(0, std::min(v, std::min(nfeatures, cap)));
+    v = std::max(0, std::min(v, std::min(o.nfeatures, o.cap)));
     total += v;
   }
-  int rc;
-  if ((rc = check_room(t, "lislam_bow_trainer_add_batch", n_scans, total))) return rc;
-  return ingest(t, reinterpret_cast<const uint4*>(desc + (size_t)first_scan * cap * 32), cap, cnt);
+  LISLAM_RC(check_room(t, who, n_scans, total));
+  return ingest(t, reinterpret_cast<const uint4*>(o.desc + (size_t)first_scan * o.cap * 32), o.cap, cnt);
 }
 
 int lislam_bow_train(lislam_bow_trainer* t, const lislam_bow_train_config* cfg, int32_t* n_nodes_out,
@@ -1390,8 +1314,8 @@ int lislam_bow_train(lislam_bow_trainer* t, const lislam_bow_train_config* cfg, 
   lislam_bow_train_config d = {10, 5, 100, 0};
   if (cfg) d = *cfg;
   if (d.k < 2 || d.k > kMaxChildren || d.L < 1 || d.L > LISLAM_BOW_TRAIN_MAX_L || d.max_iterations < 1)
-    return bfail(c, LISLAM_ERR_ARG, "lislam_bow_train: k 2..%d, L 1..%d, max_iterations >= 1 (got %d, %d, %d)", kMaxChildren,
-                 LISLAM_BOW_TRAIN_MAX_L, d.k, d.L, d.max_iterations);
+    return fail(c, LISLAM_ERR_ARG, "lislam_bow_train: k 2..%d, L 1..%d, max_iterations >= 1 (got %d, %d, %d)", kMaxChildren,
+                LISLAM_BOW_TRAIN_MAX_L, d.k, d.L, d.max_iterations);
   hipSetDevice(c->device);
   using clk = std::chrono::steady_clock;
   const auto ms_since = [](clk::time_point t0) { return std::chrono::duration<double, std::milli>(clk::now() - t0).count(); };
@@ -1404,18 +1328,21 @@ int lislam_bow_train(lislam_bow_trainer* t, const lislam_bow_train_config* cfg, 
   nodes[0].parent = -1;
   memset(nodes[0].desc, 0, 32);
   int rc;
-  if ((rc = treserve(c, &t->perm, (size_t)n * 2 * sizeof(int))) || (rc = treserve(c, &t->slot, (size_t)n)) ||
-      (rc = treserve(c, &t->mind, (size_t)n * sizeof(int))) || (rc = treserve(c, &t->node_of, (size_t)n * sizeof(int))) ||
-      (rc = treserve(c, &t->scalars, 16)))
-    return rc;
+  // never a null buffer, whatever the size
+  const auto room = [c](DBuf& b, size_t want) { return b.reserve(std::max<size_t>(want, 16), c->stream); };
+  LISLAM_HIPCHK(c, room(t->perm, (size_t)n * 2 * sizeof(int)));
+  LISLAM_HIPCHK(c, room(t->slot, (size_t)n));
+  LISLAM_HIPCHK(c, room(t->mind, (size_t)n * sizeof(int)));
+  LISLAM_HIPCHK(c, room(t->node_of, (size_t)n * sizeof(int)));
+  LISLAM_HIPCHK(c, room(t->scalars, 16));
   int* perm_a = static_cast<int*>(t->perm.p);
   int* perm_b = perm_a + n;
   int* d_changed = static_cast<int*>(t->scalars.p);
   {
     std::vector<int> iota(n);
     for (int i = 0; i < n; i++) iota[i] = i;
-    if (n) BCHK(c, hipMemcpyAsync(perm_a, iota.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    BCHK(c, hipStreamSynchronize(c->stream));
+    if (n) LISLAM_HIPCHK(c, hipMemcpyAsync(perm_a, iota.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    LISLAM_HIPCHK(c, hipStreamSynchronize(c->stream));
   }
   // the nodes to cluster at this level, in the order of their segments
   std::vector<int> a_start, a_cnt, a_node;
@@ -1432,7 +1359,7 @@ int lislam_bow_train(lislam_bow_trainer* t, const lislam_bow_train_config* cfg, 
     auto t_phase = clk::now();
     const auto phase = [&](int which) -> int {  // with profile: wait, and book the time since the last phase ended
       if (!profile) return LISLAM_OK;
-      BCHK(c, hipStreamSynchronize(c->stream));
+      LISLAM_HIPCHK(c, hipStreamSynchronize(c->stream));
       st.phase_ms[level - 1][which] += ms_since(t_phase);
       t_phase = clk::now();
       return LISLAM_OK;
@@ -1465,10 +1392,11 @@ int lislam_bow_train(lislam_bow_trainer* t, const lislam_bow_train_config* cfg, 
     // the level's arrays in one buffer: key | start cnt coff tile0 big ncent last big_node toff | tile
     const size_t lvl_bytes = (size_t)A * 8 + ((size_t)A * 7 + B + T) * 4 + (size_t)T * 8 + 64;
     const size_t gbytes = (size_t)B * k * (kThreads + 1) * sizeof(uint32_t);
-    if ((rc = treserve(c, &t->lvl, lvl_bytes)) || (rc = treserve(c, &t->centre, (size_t)rows * 32)) ||
-        (rc = treserve(c, &t->tcount, trows * sizeof(int))) || (rc = treserve(c, &t->childcnt, (size_t)rows * sizeof(int))) ||
-        (rc = treserve(c, &t->gcount, gbytes)))
-      return rc;
+    LISLAM_HIPCHK(c, room(t->lvl, lvl_bytes));
+    LISLAM_HIPCHK(c, room(t->centre, (size_t)rows * 32));
+    LISLAM_HIPCHK(c, room(t->tcount, trows * sizeof(int)));
+    LISLAM_HIPCHK(c, room(t->childcnt, (size_t)rows * sizeof(int)));
+    LISLAM_HIPCHK(c, room(t->gcount, gbytes));
     uint64_t* d_key = static_cast<uint64_t*>(t->lvl.p);
     int2* d_tile = reinterpret_cast<int2*>(d_key + A);
     int* d_start = reinterpret_cast<int*>(d_tile + T);
@@ -1477,15 +1405,15 @@ int lislam_bow_train(lislam_bow_trainer* t, const lislam_bow_train_config* cfg, 
     const auto up = [&](void* dst, const void* src, size_t bytes) {
       return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream) : hipSuccess;
     };
-    BCHK(c, up(d_key, a_key.data(), (size_t)A * 8));
-    BCHK(c, up(d_tile, tile.data(), (size_t)T * 8));
-    BCHK(c, up(d_start, a_start.data(), (size_t)A * 4));
-    BCHK(c, up(d_cnt, a_cnt.data(), (size_t)A * 4));
-    BCHK(c, up(d_coff, coff.data(), (size_t)A * 4));
-    BCHK(c, up(d_tile0, tile0.data(), (size_t)A * 4));
-    BCHK(c, up(d_big, big.data(), (size_t)A * 4));
-    BCHK(c, up(d_big_node, big_node.data(), (size_t)B * 4));
-    BCHK(c, up(d_toff, toff.data(), (size_t)T * 4));
+    LISLAM_HIPCHK(c, up(d_key, a_key.data(), (size_t)A * 8));
+    LISLAM_HIPCHK(c, up(d_tile, tile.data(), (size_t)T * 8));
+    LISLAM_HIPCHK(c, up(d_start, a_start.data(), (size_t)A * 4));
+    LISLAM_HIPCHK(c, up(d_cnt, a_cnt.data(), (size_t)A * 4));
+    LISLAM_HIPCHK(c, up(d_coff, coff.data(), (size_t)A * 4));
+    LISLAM_HIPCHK(c, up(d_tile0, tile0.data(), (size_t)A * 4));
+    LISLAM_HIPCHK(c, up(d_big, big.data(), (size_t)A * 4));
+    LISLAM_HIPCHK(c, up(d_big_node, big_node.data(), (size_t)B * 4));
+    LISLAM_HIPCHK(c, up(d_toff, toff.data(), (size_t)T * 4));
     const Level lv{d_start, d_cnt, d_key, d_coff, d_tile0, d_big, d_ncent, d_last, static_cast<uint32_t*>(t->centre.p), A, k};
     const Work w{static_cast<const uint4*>(t->desc), perm_a, perm_b, static_cast<uint8_t*>(t->slot.p), static_cast<int*>(t->mind.p),
                  static_cast<int*>(t->node_of.p), n};
@@ -1494,24 +1422,24 @@ int lislam_bow_train(lislam_bow_trainer* t, const lislam_bow_train_config* cfg, 
     hipLaunchKernelGGL(k_bowt_locate, flat, dim3(kThreads), 0, c->stream, lv, w);
     if (max_cnt > kSeedWide) hipLaunchKernelGGL(k_bowt_seed<1024>, dim3(A), dim3(1024), 0, c->stream, lv, w);
     else hipLaunchKernelGGL(k_bowt_seed<kThreads>, dim3(A), dim3(kThreads), 0, c->stream, lv, w);
-    BCHK(c, hipGetLastError());
+    LISLAM_HIPCHK(c, hipGetLastError());
     if ((rc = phase(LISLAM_BOW_PHASE_SEED))) return rc;
     if (n_kmeans) {
       hipLaunchKernelGGL(k_bowt_assign, flat, dim3(kThreads), 0, c->stream, lv, w, 1, d_changed);
       if ((rc = phase(LISLAM_BOW_PHASE_ASSIGN))) return rc;
       for (int it = 2; it <= d.max_iterations; it++) {  // bounded by the cap; the host reads the level's "changed" word
-        BCHK(c, hipMemsetAsync(d_changed, 0, sizeof(int), c->stream));
-        if (B) BCHK(c, hipMemsetAsync(t->gcount.p, 0, gbytes, c->stream));
+        LISLAM_HIPCHK(c, hipMemsetAsync(d_changed, 0, sizeof(int), c->stream));
+        if (B) LISLAM_HIPCHK(c, hipMemsetAsync(t->gcount.p, 0, gbytes, c->stream));
         hipLaunchKernelGGL(k_bowt_means, dim3(T), dim3(kMeansThreads), 0, c->stream, lv, w, tl, static_cast<uint32_t*>(t->gcount.p));
         if (B)
           hipLaunchKernelGGL(k_bowt_majority, dim3(k, B), dim3(kThreads), 0, c->stream, lv, d_big_node,
                              static_cast<const uint32_t*>(t->gcount.p));
         if ((rc = phase(LISLAM_BOW_PHASE_MEANS))) return rc;
         hipLaunchKernelGGL(k_bowt_assign, flat, dim3(kThreads), 0, c->stream, lv, w, it, d_changed);
-        BCHK(c, hipGetLastError());
+        LISLAM_HIPCHK(c, hipGetLastError());
         int changed = 0;
-        BCHK(c, hipMemcpyAsync(&changed, d_changed, sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        BCHK(c, hipStreamSynchronize(c->stream));
+        LISLAM_HIPCHK(c, hipMemcpyAsync(&changed, d_changed, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        LISLAM_HIPCHK(c, hipStreamSynchronize(c->stream));
         if ((rc = phase(LISLAM_BOW_PHASE_ASSIGN))) return rc;
         if (changed == 0) break;
       }
@@ -1519,16 +1447,16 @@ int lislam_bow_train(lislam_bow_trainer* t, const lislam_bow_train_config* cfg, 
     hipLaunchKernelGGL(k_bowt_tilecount, dim3(T), dim3(kThreads), 0, c->stream, lv, w, tl);
     hipLaunchKernelGGL(k_bowt_offsets, dim3(A), dim3(64), 0, c->stream, lv, tl);
     hipLaunchKernelGGL(k_bowt_scatter, dim3(T), dim3(kThreads), 0, c->stream, lv, w, tl);
-    BCHK(c, hipGetLastError());
+    LISLAM_HIPCHK(c, hipGetLastError());
     // only the segments clustered at this level are written to the other buffer: every later level reads
     // inside them, never the positions of a node that is finished
     std::vector<int> ncent(A), last(A), childcnt(rows);
     std::vector<uint8_t> centre((size_t)rows * 32);
-    BCHK(c, hipMemcpyAsync(ncent.data(), d_ncent, (size_t)A * 4, hipMemcpyDeviceToHost, c->stream));
-    BCHK(c, hipMemcpyAsync(last.data(), d_last, (size_t)A * 4, hipMemcpyDeviceToHost, c->stream));
-    BCHK(c, hipMemcpyAsync(childcnt.data(), t->childcnt.p, (size_t)rows * 4, hipMemcpyDeviceToHost, c->stream));
-    BCHK(c, hipMemcpyAsync(centre.data(), t->centre.p, (size_t)rows * 32, hipMemcpyDeviceToHost, c->stream));
-    BCHK(c, hipStreamSynchronize(c->stream));
+    LISLAM_HIPCHK(c, hipMemcpyAsync(ncent.data(), d_ncent, (size_t)A * 4, hipMemcpyDeviceToHost, c->stream));
+    LISLAM_HIPCHK(c, hipMemcpyAsync(last.data(), d_last, (size_t)A * 4, hipMemcpyDeviceToHost, c->stream));
+    LISLAM_HIPCHK(c, hipMemcpyAsync(childcnt.data(), t->childcnt.p, (size_t)rows * 4, hipMemcpyDeviceToHost, c->stream));
+    LISLAM_HIPCHK(c, hipMemcpyAsync(centre.data(), t->centre.p, (size_t)rows * 32, hipMemcpyDeviceToHost, c->stream));
+    LISLAM_HIPCHK(c, hipStreamSynchronize(c->stream));
     if ((rc = phase(LISLAM_BOW_PHASE_PARTITION))) return rc;
     std::swap(perm_a, perm_b);
     std::vector<int> n_start, n_cnt, n_node;
@@ -1623,19 +1551,19 @@ int lislam_bow_train(lislam_bow_trainer* t, const lislam_bow_train_config* cfg, 
       max_children = std::max(max_children, nodes[q].n_child);
     }
     const size_t tree_bytes = (size_t)N * 40 + (size_t)n_words * 8 + 16;
-    if ((rc = treserve(c, &t->tree, tree_bytes)) || (rc = treserve(c, &t->words, ((size_t)n + n_words) * sizeof(int))))
-      return rc;
+    LISLAM_HIPCHK(c, room(t->tree, tree_bytes));
+    LISLAM_HIPCHK(c, room(t->words, ((size_t)n + n_words) * sizeof(int)));
     uint4* d_td = static_cast<uint4*>(t->tree.p);
     int2* d_tn = reinterpret_cast<int2*>(d_td + (size_t)N * 2);
     double* d_tw = reinterpret_cast<double*>(d_tn + N);
     int* d_n = reinterpret_cast<int*>(d_tw + n_words);
     int* d_words = static_cast<int*>(t->words.p);
     int* d_ni = d_words + n;
-    BCHK(c, hipMemcpyAsync(d_td, td.data(), td.size(), hipMemcpyHostToDevice, c->stream));
-    BCHK(c, hipMemcpyAsync(d_tn, tn.data(), (size_t)N * 8, hipMemcpyHostToDevice, c->stream));
-    BCHK(c, hipMemsetAsync(d_tw, 0, (size_t)n_words * 8, c->stream));
-    BCHK(c, hipMemcpyAsync(d_n, &n, sizeof(int), hipMemcpyHostToDevice, c->stream));
-    BCHK(c, hipMemsetAsync(d_ni, 0, (size_t)n_words * sizeof(int), c->stream));
+    LISLAM_HIPCHK(c, hipMemcpyAsync(d_td, td.data(), td.size(), hipMemcpyHostToDevice, c->stream));
+    LISLAM_HIPCHK(c, hipMemcpyAsync(d_tn, tn.data(), (size_t)N * 8, hipMemcpyHostToDevice, c->stream));
+    LISLAM_HIPCHK(c, hipMemsetAsync(d_tw, 0, (size_t)n_words * 8, c->stream));
+    LISLAM_HIPCHK(c, hipMemcpyAsync(d_n, &n, sizeof(int), hipMemcpyHostToDevice, c->stream));
+    LISLAM_HIPCHK(c, hipMemsetAsync(d_ni, 0, (size_t)n_words * sizeof(int), c->stream));
     const Tree tree{d_tn, d_td, d_tw, depth};
     const Source src{static_cast<const uint4*>(t->desc), nullptr, d_n, 0, 1, n, n};
     if (max_children <= 16)
@@ -1644,23 +1572,23 @@ int lislam_bow_train(lislam_bow_trainer* t, const lislam_bow_train_config* cfg, 
     else
       hipLaunchKernelGGL(k_bow_words<64>, dim3((unsigned)(((long long)n * 64 + kThreads - 1) / kThreads)), dim3(kThreads), 0,
                          c->stream, tree, src, d_words, (double*)nullptr);
-    BCHK(c, hipGetLastError());
+    LISLAM_HIPCHK(c, hipGetLastError());
     // the bitmap holds (images of a pass) x (words) bits
     const int row_words = (n_words + 31) / 32;
     const int per_pass = (int)std::max<size_t>(1, std::min<size_t>((size_t)t->n_images, kBitmapBytes / 4 / (size_t)row_words));
-    if ((rc = treserve(c, &t->bitmap, (size_t)per_pass * row_words * 4))) return rc;
+    LISLAM_HIPCHK(c, room(t->bitmap, (size_t)per_pass * row_words * 4));
     for (int m0 = 0; m0 < t->n_images; m0 += per_pass) {
       const int m1 = std::min(t->n_images, m0 + per_pass);
       const int i0 = t->img_off[m0], i1 = t->img_off[m1];
       if (i1 == i0) continue;
-      BCHK(c, hipMemsetAsync(t->bitmap.p, 0, (size_t)(m1 - m0) * row_words * 4, c->stream));
+      LISLAM_HIPCHK(c, hipMemsetAsync(t->bitmap.p, 0, (size_t)(m1 - m0) * row_words * 4, c->stream));
       hipLaunchKernelGGL(k_bowt_ni, dim3((i1 - i0 + kThreads - 1) / kThreads), dim3(kThreads), 0, c->stream, d_words,
                          static_cast<const int*>(t->img_of), i0, i1, m0, row_words, static_cast<uint32_t*>(t->bitmap.p), d_ni);
     }
-    BCHK(c, hipGetLastError());
+    LISLAM_HIPCHK(c, hipGetLastError());
     std::vector<int> ni(n_words);
-    BCHK(c, hipMemcpyAsync(ni.data(), d_ni, (size_t)n_words * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    BCHK(c, hipStreamSynchronize(c->stream));
+    LISLAM_HIPCHK(c, hipMemcpyAsync(ni.data(), d_ni, (size_t)n_words * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    LISLAM_HIPCHK(c, hipStreamSynchronize(c->stream));
     for (int wd = 0; wd < n_words; wd++) {
       if (ni[wd] > 0) t->weight[word_node[wd]] = std::log((double)t->n_images / (double)ni[wd]);
       st.n_zero_words += t->weight[word_node[wd]] == 0.0;
@@ -1677,10 +1605,10 @@ int lislam_bow_train(lislam_bow_trainer* t, const lislam_bow_train_config* cfg, 
 int lislam_bow_trainer_vocabulary(lislam_bow_trainer* t, int32_t cap_nodes, int32_t* parent, uint8_t* descriptor,
                                   double* weight) {
   if (!t) return LISLAM_ERR_ARG;
-  if (!t->trained) return bfail(t->ctx, LISLAM_ERR_STATE, "lislam_bow_trainer_vocabulary: run lislam_bow_train first");
+  if (!t->trained) return fail(t->ctx, LISLAM_ERR_STATE, "lislam_bow_trainer_vocabulary: run lislam_bow_train first");
   const size_t N = t->parent.size();
   if (cap_nodes < 0 || (size_t)cap_nodes < N)
-    return bfail(t->ctx, LISLAM_ERR_CAPACITY, "lislam_bow_trainer_vocabulary: %zu nodes, capacity %d", N, cap_nodes);
+    return fail(t->ctx, LISLAM_ERR_CAPACITY, "lislam_bow_trainer_vocabulary: %zu nodes, capacity %d", N, cap_nodes);
   if (parent) memcpy(parent, t->parent.data(), N * sizeof(int32_t));
   if (descriptor) memcpy(descriptor, t->descriptor.data(), N * 32);
   if (weight) memcpy(weight, t->weight.data(), N * sizeof(double));

@@ -32,6 +32,7 @@
 #include "lislam_batch.hpp"
 #include "lislam_ctx.hpp"
 #include "lislam_device.hpp"
+#include "lislam_host.hpp"
 
 namespace lislam {
 namespace ground {
@@ -497,11 +498,6 @@ using lislam::ground::Engine;
 
 void lislam_free_ground(void* p) { delete static_cast<Engine*>(p); }
 
-static int gfail(lislam_ctx* c, int code, const char* msg) {
-  if (c) c->err = msg;
-  return code;
-}
-
 // Ground outputs of one scan of a batch (lislam_batch_download).
 int lislam_ground_batch_output(lislam_batch* b, int what, int scan, const void** src, int* cnt, size_t* esz) {
   const Engine* e = static_cast<const Engine*>(b->ground);
@@ -541,7 +537,7 @@ extern "C" int lislam_batch_ground(lislam_batch* b, int32_t n_scans) {
     }
     if (!ok) {
       delete e;
-      return gfail(c, LISLAM_ERR_DEVICE, "lislam_batch_ground: device allocation failed");
+      return lislam::fail(c, LISLAM_ERR_DEVICE, "lislam_batch_ground: device allocation failed");
     }
     b->ground = e;
   }
@@ -564,6 +560,6 @@ extern "C" int lislam_batch_ground(lislam_batch* b, int32_t n_scans) {
     TimedScope t(c, kT_ground_extract);
     hipLaunchKernelGGL(lislam::ground::k_ground_extract, dim3(n_scans), dim3(lislam::ground::kThreads), 0, st, a);
   }
-  if (hipGetLastError() != hipSuccess) return gfail(c, LISLAM_ERR_DEVICE, "lislam_batch_ground: launch failed");
+  if (hipGetLastError() != hipSuccess) return lislam::fail(c, LISLAM_ERR_DEVICE, "lislam_batch_ground: launch failed");
   return LISLAM_OK;
 }

@@ -31,6 +31,7 @@
 #include "lislam_batch.hpp"
 #include "lislam_ctx.hpp"
 #include "lislam_device.hpp"
+#include "lislam_host.hpp"
 
 namespace lislam {
 namespace keysel {
@@ -191,54 +192,21 @@ __global__ __launch_bounds__(kChunk) void k_keysel(Args a) {
 }  // namespace lislam
 
 using namespace lislam::keysel;
+using lislam::DBuf;
+using lislam::fail;
 
 struct lislam_keysel {
   lislam_ctx* ctx = nullptr;
   lislam_keysel_config cfg{};
   State* st = nullptr;
   // grow-only staging: [T_s2s n x 7][time n][good n] in, [T_s2m n x 16][node n x 26][id n][n_selected] out
-  void* in = nullptr;
-  size_t in_bytes = 0;
-  void* out = nullptr;
-  size_t out_bytes = 0;
+  DBuf in, out;
 };
 
 namespace {
 
-int kfail(lislam_ctx* c, int code, const char* fmt, ...) {
-  if (c) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    c->err = buf;
-  }
-  return code;
-}
-
-#define KCHK(ctx, x)                                                                                  \
-  do {                                                                                                \
-    hipError_t e_ = (x);                                                                              \
-    if (e_ != hipSuccess) return kfail(ctx, LISLAM_ERR_DEVICE, "%s: %s", #x, hipGetErrorString(e_)); \
-  } while (0)
-
-int reserve(lislam_ctx* c, void** p, size_t* have, size_t want) {
-  if (want <= *have) return LISLAM_OK;
-  if (*p) {
-    KCHK(c, hipStreamSynchronize(c->stream));
-    (void)hipFree(*p);
-    *p = nullptr;
-    *have = 0;
-  }
-  KCHK(c, hipMalloc(p, want));
-  *have = want;
-  return LISLAM_OK;
-}
-
 void free_keysel(lislam_keysel* s) {
-  for (void* q : {(void*)s->st, s->in, s->out})
-    if (q) (void)hipFree(q);
+  if (s->st) (void)hipFree(s->st);
   delete s;
 }
 
@@ -247,25 +215,24 @@ int run(lislam_keysel* s, const double* d_T, const int* d_good, int good_stride,
         int32_t* keyframe_id, int32_t* n_selected, double* T_s2m, double* node) {
   lislam_ctx* c = s->ctx;
   const size_t N = (size_t)n;
-  int rc;
-  if ((rc = reserve(c, &s->out, &s->out_bytes, N * (16 + kNode) * 8 + (N + 1) * 4))) return rc;
-  double* d_Tm = static_cast<double*>(s->out);
+  LISLAM_HIPCHK(c, s->out.reserve(N * (16 + kNode) * 8 + (N + 1) * 4, c->stream));
+  double* d_Tm = s->out.as<double>();
   double* d_node = d_Tm + N * 16;
   int* d_id = reinterpret_cast<int*>(d_node + N * kNode);
   int* d_nsel = d_id + N;
   const Args a{d_T, d_good, good_stride, d_time, n, s->cfg.time_interval, s->cfg.distance_interval, s->st, d_id, d_nsel,
                T_s2m ? d_Tm : nullptr, node ? d_node : nullptr};
   hipLaunchKernelGGL(k_keysel, dim3(1), dim3(kChunk), 0, c->stream, a);
-  KCHK(c, hipGetLastError());
+  LISLAM_HIPCHK(c, hipGetLastError());
   int nsel = 0;
-  if (keyframe_id) KCHK(c, hipMemcpyAsync(keyframe_id, d_id, N * 4, hipMemcpyDeviceToHost, c->stream));
-  if (T_s2m) KCHK(c, hipMemcpyAsync(T_s2m, d_Tm, N * 16 * 8, hipMemcpyDeviceToHost, c->stream));
-  KCHK(c, hipMemcpyAsync(&nsel, d_nsel, 4, hipMemcpyDeviceToHost, c->stream));
-  KCHK(c, hipStreamSynchronize(c->stream));
+  if (keyframe_id) LISLAM_HIPCHK(c, hipMemcpyAsync(keyframe_id, d_id, N * 4, hipMemcpyDeviceToHost, c->stream));
+  if (T_s2m) LISLAM_HIPCHK(c, hipMemcpyAsync(T_s2m, d_Tm, N * 16 * 8, hipMemcpyDeviceToHost, c->stream));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(&nsel, d_nsel, 4, hipMemcpyDeviceToHost, c->stream));
+  LISLAM_HIPCHK(c, hipStreamSynchronize(c->stream));
   if (n_selected) *n_selected = nsel;
   if (node && nsel > 0) {
-    KCHK(c, hipMemcpyAsync(node, d_node, (size_t)nsel * kNode * 8, hipMemcpyDeviceToHost, c->stream));
-    KCHK(c, hipStreamSynchronize(c->stream));
+    LISLAM_HIPCHK(c, hipMemcpyAsync(node, d_node, (size_t)nsel * kNode * 8, hipMemcpyDeviceToHost, c->stream));
+    LISLAM_HIPCHK(c, hipStreamSynchronize(c->stream));
   }
   return LISLAM_OK;
 }
@@ -280,7 +247,7 @@ int lislam_keysel_create(lislam_ctx* c, const lislam_keysel_config* cfg, lislam_
   lislam_keysel_config d = {0.3, 0.3};  // config/spot.yaml:35-36
   if (cfg) d = *cfg;
   if (std::isnan(d.time_interval) || std::isnan(d.distance_interval))
-    return kfail(c, LISLAM_ERR_ARG, "lislam_keysel_create: the intervals must be numbers");
+    return fail(c, LISLAM_ERR_ARG, "lislam_keysel_create: the intervals must be numbers");
   hipSetDevice(c->device);
   lislam_keysel* s = new lislam_keysel();
   s->ctx = c;
@@ -293,7 +260,7 @@ int lislam_keysel_create(lislam_ctx* c, const lislam_keysel_config* cfg, lislam_
       hipStreamSynchronize(c->stream) != hipSuccess) {  // h leaves scope
     (void)hipGetLastError();
     free_keysel(s);
-    return kfail(c, LISLAM_ERR_DEVICE, "lislam_keysel_create: device allocation failed");
+    return fail(c, LISLAM_ERR_DEVICE, "lislam_keysel_create: device allocation failed");
   }
   *out = s;
   return LISLAM_OK;
@@ -317,15 +284,14 @@ int lislam_keysel_step(lislam_keysel* s, const double* T_s2s, const int32_t* goo
   }
   hipSetDevice(c->device);
   const size_t N = (size_t)n;
-  int rc;
-  if ((rc = reserve(c, &s->in, &s->in_bytes, N * 8 * 8 + N * 4))) return rc;
-  double* d_T = static_cast<double*>(s->in);
+  LISLAM_HIPCHK(c, s->in.reserve(N * 8 * 8 + N * 4, c->stream));
+  double* d_T = s->in.as<double>();
   double* d_time = d_T + N * 7;
   int* d_good = reinterpret_cast<int*>(d_time + N);
   // pageable sources: these copies have read them when they return
-  KCHK(c, hipMemcpyAsync(d_T, T_s2s, N * 7 * 8, hipMemcpyDefault, c->stream));
-  KCHK(c, hipMemcpyAsync(d_good, good, N * 4, hipMemcpyDefault, c->stream));
-  KCHK(c, hipMemcpyAsync(d_time, time, N * 8, hipMemcpyHostToDevice, c->stream));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(d_T, T_s2s, N * 7 * 8, hipMemcpyDefault, c->stream));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(d_good, good, N * 4, hipMemcpyDefault, c->stream));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(d_time, time, N * 8, hipMemcpyHostToDevice, c->stream));
   return run(s, d_T, d_good, 1, d_time, n, keyframe_id, n_selected, T_s2m, node);
 }
 
@@ -333,20 +299,12 @@ int lislam_keysel_step_batch(lislam_keysel* s, lislam_batch* b, int32_t first_sc
                              int32_t* keyframe_id, int32_t* n_selected, double* T_s2m, double* node) {
   if (!s || !b) return LISLAM_ERR_ARG;
   lislam_ctx* c = s->ctx;
-  if (b->ctx != c) return kfail(c, LISLAM_ERR_ARG, "lislam_keysel_step_batch: the batch belongs to another context");
-  if (first_scan < 0 || n_scans < 0 || (int64_t)first_scan + n_scans > b->max_scans)
-    return kfail(c, LISLAM_ERR_ARG, "lislam_keysel_step_batch: scans [%d, %d + %d) out of range", first_scan, first_scan,
-                 n_scans);
-  if (n_scans > 0 && !time) return kfail(c, LISLAM_ERR_ARG, "lislam_keysel_step_batch: null time");
-  // the settling path of lislam_bow_add_batch: a device-decided cascade's verdict is final after it
-  const uint8_t* desc = nullptr;
-  const int* counts = nullptr;
-  int cap = 0, nfeatures = 0, ran = 0;
-  int rc = lislam_orb_batch_descriptors(b, &desc, &counts, &cap, &nfeatures, &ran);
-  if (rc == LISLAM_ERR_STATE || (rc == LISLAM_OK && first_scan + n_scans > ran))
-    return kfail(c, LISLAM_ERR_STATE, "lislam_keysel_step_batch: run lislam_batch_intensity_odometry over %d scans first",
-                 first_scan + n_scans);
-  if (rc) return rc;
+  const char* who = "lislam_keysel_step_batch";
+  LISLAM_RC(lislam::check_same_context(c, who, b));
+  LISLAM_RC(lislam::check_scan_range(c, who, b, first_scan, n_scans));
+  if (n_scans > 0 && !time) return fail(c, LISLAM_ERR_ARG, "lislam_keysel_step_batch: null time");
+  lislam::OrbDescriptors o;  // not read: the call settles a device-decided cascade, whose verdict is final after it
+  LISLAM_RC(lislam::orb_descriptors(c, who, b, first_scan + n_scans, &o));
   if (n_scans == 0) {
     if (n_selected) *n_selected = 0;
     return LISLAM_OK;
@@ -354,13 +312,13 @@ int lislam_keysel_step_batch(lislam_keysel* s, lislam_batch* b, int32_t first_sc
   const void *src_T = nullptr, *src_S = nullptr;
   int cnt = 0;
   size_t esz = 0;
-  if ((rc = lislam_orb_batch_output(b, LISLAM_OUT_ORB_T, first_scan, &src_T, &cnt, &esz))) return rc;
-  if ((rc = lislam_orb_batch_output(b, LISLAM_OUT_ORB_STATS, first_scan, &src_S, &cnt, &esz))) return rc;
+  LISLAM_RC(lislam_orb_batch_output(b, LISLAM_OUT_ORB_T, first_scan, &src_T, &cnt, &esz));
+  LISLAM_RC(lislam_orb_batch_output(b, LISLAM_OUT_ORB_STATS, first_scan, &src_S, &cnt, &esz));
   hipSetDevice(c->device);
   const size_t N = (size_t)n_scans;
-  if ((rc = reserve(c, &s->in, &s->in_bytes, N * 8 * 8 + N * 4))) return rc;
-  double* d_time = static_cast<double*>(s->in) + N * 7;
-  KCHK(c, hipMemcpyAsync(d_time, time, N * 8, hipMemcpyHostToDevice, c->stream));
+  LISLAM_HIPCHK(c, s->in.reserve(N * 8 * 8 + N * 4, c->stream));
+  double* d_time = s->in.as<double>() + N * 7;
+  LISLAM_HIPCHK(c, hipMemcpyAsync(d_time, time, N * 8, hipMemcpyHostToDevice, c->stream));
   return run(s, static_cast<const double*>(src_T), static_cast<const int*>(src_S), 8, d_time, n_scans, keyframe_id, n_selected,
              T_s2m, node);
 }
@@ -370,8 +328,8 @@ int lislam_keysel_state(lislam_keysel* s, int32_t* n_keyframes, double* T_s2m16,
   lislam_ctx* c = s->ctx;
   hipSetDevice(c->device);
   State h;
-  KCHK(c, hipMemcpyAsync(&h, s->st, sizeof(State), hipMemcpyDeviceToHost, c->stream));
-  KCHK(c, hipStreamSynchronize(c->stream));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(&h, s->st, sizeof(State), hipMemcpyDeviceToHost, c->stream));
+  LISLAM_HIPCHK(c, hipStreamSynchronize(c->stream));
   if (n_keyframes) *n_keyframes = h.next_id;
   if (T_s2m16) std::copy(h.T, h.T + 16, T_s2m16);
   if (last_time) *last_time = h.last_time;

@@ -36,6 +36,7 @@
 #include "lislam_batch.hpp"
 #include "lislam_ctx.hpp"
 #include "lislam_device.hpp"
+#include "lislam_host.hpp"
 #include "lislam_lm.hpp"
 #include "lislam_lm_wave.hpp"
 #include "lislam_mapwin.hpp"
@@ -1217,50 +1218,7 @@ using namespace lislam::mapk;
 
 namespace {
 
-int mfail(lislam_ctx* c, int code, const char* fmt, ...) {
-  if (c) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    c->err = buf;
-  }
-  return code;
-}
-
-#define MCHK(ctx, x)                                                                          \
-  do {                                                                                        \
-    hipError_t e_ = (x);                                                                      \
-    if (e_ != hipSuccess) return mfail(ctx, LISLAM_ERR_DEVICE, "%s: %s", #x, hipGetErrorString(e_)); \
-  } while (0)
-
-#define MRC(x)                    \
-  do {                            \
-    int rc_ = (x);                \
-    if (rc_ != LISLAM_OK) return rc_; \
-  } while (0)
-
 inline int blocks(int64_t n, int t = 256) { return (int)std::max<int64_t>(1, (n + t - 1) / t); }
-
-// Growable device buffer.
-struct DBuf {
-  void* p = nullptr;
-  size_t bytes = 0;
-  ~DBuf() { if (p) (void)hipFree(p); }
-  hipError_t reserve(size_t b) {
-    if (b <= bytes) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    bytes = 0;
-    const size_t nb = std::max<size_t>(b, 256) + b / 4;
-    hipError_t e = hipMalloc(&p, nb);
-    if (e == hipSuccess) bytes = nb;
-    return e;
-  }
-  template <typename T>
-  T* as() const { return static_cast<T*>(p); }
-};
 
 uint32_t pow2_at_least(uint64_t v) {
   uint32_t c = 1024;
@@ -1311,13 +1269,13 @@ hipStream_t stream_of(lislam_ctx* c) { return c->stream; }
 
 // Stable radix sort of (u64 / u32 key, int) pairs (lislam_prims.hpp); ki / vi are clobbered.
 int sort_pairs_u64(lislam_ctx* c, DBuf& tmp, uint64_t* ki, uint64_t* ko, int* vi, int* vo, int n) {
-  MCHK(c, tmp.reserve(prims::sort_temp_bytes(n)));
-  MCHK(c, prims::sort_pairs<uint64_t>(tmp.p, ki, ko, vi, vo, n, 64, stream_of(c)));
+  LISLAM_HIPCHK(c, tmp.reserve(prims::sort_temp_bytes(n)));
+  LISLAM_HIPCHK(c, prims::sort_pairs<uint64_t>(tmp.p, ki, ko, vi, vo, n, 64, stream_of(c)));
   return LISLAM_OK;
 }
 int sort_pairs_u32(lislam_ctx* c, DBuf& tmp, uint32_t* ki, uint32_t* ko, int* vi, int* vo, int n) {
-  MCHK(c, tmp.reserve(prims::sort_temp_bytes(n)));
-  MCHK(c, prims::sort_pairs<uint32_t>(tmp.p, ki, ko, vi, vo, n, 32, stream_of(c)));
+  LISLAM_HIPCHK(c, tmp.reserve(prims::sort_temp_bytes(n)));
+  LISLAM_HIPCHK(c, prims::sort_pairs<uint32_t>(tmp.p, ki, ko, vi, vo, n, 32, stream_of(c)));
   return LISLAM_OK;
 }
 
@@ -1326,33 +1284,33 @@ int rebuild(lislam_map* m, int64_t n) {
   lislam_ctx* c = m->ctx;
   hipStream_t st = stream_of(c);
   m->n = n;
-  MCHK(c, m->pts.reserve(std::max<int64_t>(n, 1) * sizeof(float4)));
+  LISLAM_HIPCHK(c, m->pts.reserve(std::max<int64_t>(n, 1) * sizeof(float4)));
   if (n == 0) { m->hcap = 0; return LISLAM_OK; }
-  MCHK(c, m->keys.reserve(n * 8));
-  MCHK(c, m->keys2.reserve(n * 8));
-  MCHK(c, m->idx.reserve(n * 4));
-  MCHK(c, m->idx2.reserve(n * 4));
-  MCHK(c, m->counter.reserve(16));
+  LISLAM_HIPCHK(c, m->keys.reserve(n * 8));
+  LISLAM_HIPCHK(c, m->keys2.reserve(n * 8));
+  LISLAM_HIPCHK(c, m->idx.reserve(n * 4));
+  LISLAM_HIPCHK(c, m->idx2.reserve(n * 4));
+  LISLAM_HIPCHK(c, m->counter.reserve(16));
   const float inv = 1.0f / m->cell;
   TimedScope ts(c, kT_rebuild);
   hipLaunchKernelGGL(k_cell_keys, dim3(blocks(n)), dim3(256), 0, st, m->tmp.as<float4>(), (int)n, inv,
                      m->keys.as<uint64_t>(), m->idx.as<int>());
-  MRC(sort_pairs_u64(c, m->sort_tmp, m->keys.as<uint64_t>(), m->keys2.as<uint64_t>(), m->idx.as<int>(), m->idx2.as<int>(),
-                     (int)n));
+  LISLAM_RC(sort_pairs_u64(c, m->sort_tmp, m->keys.as<uint64_t>(), m->keys2.as<uint64_t>(), m->idx.as<int>(), m->idx2.as<int>(),
+                           (int)n));
   hipLaunchKernelGGL(k_gather, dim3(blocks(n)), dim3(256), 0, st, m->tmp.as<float4>(), m->idx2.as<int>(), (int)n,
                      m->pts.as<float4>());
-  MCHK(c, hipMemsetAsync(m->counter.p, 0, sizeof(int), st));
+  LISLAM_HIPCHK(c, hipMemsetAsync(m->counter.p, 0, sizeof(int), st));
   hipLaunchKernelGGL(k_count_runs, dim3(blocks(n)), dim3(256), 0, st, m->keys2.as<uint64_t>(), (int)n, m->counter.as<int>());
   int ncell = 0;
-  MCHK(c, hipMemcpyAsync(&ncell, m->counter.p, sizeof(int), hipMemcpyDeviceToHost, st));
-  MCHK(c, hipStreamSynchronize(st));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(&ncell, m->counter.p, sizeof(int), hipMemcpyDeviceToHost, st));
+  LISLAM_HIPCHK(c, hipStreamSynchronize(st));
   m->hcap = pow2_at_least((uint64_t)ncell * 2);
-  MCHK(c, m->hkey.reserve((size_t)m->hcap * 8));
-  MCHK(c, m->hval.reserve((size_t)m->hcap * 8));
-  MCHK(c, hipMemsetAsync(m->hkey.p, 0xff, (size_t)m->hcap * 8, st));
+  LISLAM_HIPCHK(c, m->hkey.reserve((size_t)m->hcap * 8));
+  LISLAM_HIPCHK(c, m->hval.reserve((size_t)m->hcap * 8));
+  LISLAM_HIPCHK(c, hipMemsetAsync(m->hkey.p, 0xff, (size_t)m->hcap * 8, st));
   hipLaunchKernelGGL(k_insert_runs, dim3(blocks(n)), dim3(256), 0, st, m->keys2.as<uint64_t>(), (int)n,
                      m->hkey.as<uint64_t>(), m->hval.as<int2>(), m->hcap - 1);
-  MCHK(c, hipGetLastError());
+  LISLAM_HIPCHK(c, hipGetLastError());
   return LISLAM_OK;
 }
 
@@ -1361,11 +1319,11 @@ int upload_points(lislam_map* m, const float* pts, int64_t n, int stride, int id
   lislam_ctx* c = m->ctx;
   hipStream_t st = stream_of(c);
   if (n == 0) return LISLAM_OK;
-  MCHK(c, m->sc.vin.reserve((size_t)n * stride * 4));
-  MCHK(c, hipMemcpyAsync(m->sc.vin.p, pts, (size_t)n * stride * 4, hipMemcpyDefault, st));
+  LISLAM_HIPCHK(c, m->sc.vin.reserve((size_t)n * stride * 4));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(m->sc.vin.p, pts, (size_t)n * stride * 4, hipMemcpyDefault, st));
   hipLaunchKernelGGL(k_pack_points, dim3(blocks(n)), dim3(256), 0, st, m->sc.vin.as<float>(), (int)n, stride, id0,
                      dst.as<float4>() + off);
-  MCHK(c, hipGetLastError());
+  LISLAM_HIPCHK(c, hipGetLastError());
   return LISLAM_OK;
 }
 
@@ -1375,24 +1333,24 @@ int add_packed(lislam_map* m, int64_t nin, bool downsample, int64_t* n_added) {
   hipStream_t st = stream_of(c);
   const int64_t n0 = m->n;
   if (!downsample) {
-    MCHK(c, m->tmp.reserve((n0 + nin) * sizeof(float4)));
-    if (n0) MCHK(c, hipMemcpyAsync(m->tmp.p, m->pts.p, n0 * sizeof(float4), hipMemcpyDeviceToDevice, st));
-    MCHK(c, hipMemcpyAsync(m->tmp.as<float4>() + n0, m->newp.p, nin * sizeof(float4), hipMemcpyDeviceToDevice, st));
+    LISLAM_HIPCHK(c, m->tmp.reserve((n0 + nin) * sizeof(float4)));
+    if (n0) LISLAM_HIPCHK(c, hipMemcpyAsync(m->tmp.p, m->pts.p, n0 * sizeof(float4), hipMemcpyDeviceToDevice, st));
+    LISLAM_HIPCHK(c, hipMemcpyAsync(m->tmp.as<float4>() + n0, m->newp.p, nin * sizeof(float4), hipMemcpyDeviceToDevice, st));
     if (n_added) *n_added = nin;
     return rebuild(m, n0 + nin);
   }
   const uint32_t bcap = pow2_at_least((uint64_t)nin * 2);
-  MCHK(c, m->bkey.reserve((size_t)bcap * 8));
-  MCHK(c, m->bwin.reserve((size_t)bcap * 8));
-  MCHK(c, m->boxes.reserve(nin * 4));
-  MCHK(c, m->dead.reserve(std::max<int64_t>(n0, 1)));
-  MCHK(c, m->enter.reserve(nin));
-  MCHK(c, m->counter.reserve(16));
-  MCHK(c, hipMemsetAsync(m->bkey.p, 0xff, (size_t)bcap * 8, st));
-  MCHK(c, hipMemsetAsync(m->bwin.p, 0xff, (size_t)bcap * 8, st));
-  MCHK(c, hipMemsetAsync(m->dead.p, 0, std::max<int64_t>(n0, 1), st));
-  MCHK(c, hipMemsetAsync(m->enter.p, 0, nin, st));
-  MCHK(c, hipMemsetAsync(m->counter.p, 0, 16, st));
+  LISLAM_HIPCHK(c, m->bkey.reserve((size_t)bcap * 8));
+  LISLAM_HIPCHK(c, m->bwin.reserve((size_t)bcap * 8));
+  LISLAM_HIPCHK(c, m->boxes.reserve(nin * 4));
+  LISLAM_HIPCHK(c, m->dead.reserve(std::max<int64_t>(n0, 1)));
+  LISLAM_HIPCHK(c, m->enter.reserve(nin));
+  LISLAM_HIPCHK(c, m->counter.reserve(16));
+  LISLAM_HIPCHK(c, hipMemsetAsync(m->bkey.p, 0xff, (size_t)bcap * 8, st));
+  LISLAM_HIPCHK(c, hipMemsetAsync(m->bwin.p, 0xff, (size_t)bcap * 8, st));
+  LISLAM_HIPCHK(c, hipMemsetAsync(m->dead.p, 0, std::max<int64_t>(n0, 1), st));
+  LISLAM_HIPCHK(c, hipMemsetAsync(m->enter.p, 0, nin, st));
+  LISLAM_HIPCHK(c, hipMemsetAsync(m->counter.p, 0, 16, st));
   DsArgs a;
   a.m = m->view();
   a.in = m->newp.as<float4>();
@@ -1411,21 +1369,21 @@ int add_packed(lislam_map* m, int64_t nin, bool downsample, int64_t* n_added) {
     hipLaunchKernelGGL(k_ds_resolve, dim3(blocks(nin)), dim3(256), 0, st, a);
   }
   // survivors (stable) + entering inputs (input order) -> tmp
-  MCHK(c, m->tmp.reserve((n0 + nin) * sizeof(float4)));
-  MCHK(c, m->live.reserve(std::max<int64_t>(n0, 1)));
+  LISLAM_HIPCHK(c, m->tmp.reserve((n0 + nin) * sizeof(float4)));
+  LISLAM_HIPCHK(c, m->live.reserve(std::max<int64_t>(n0, 1)));
   int* nsel = m->counter.as<int>() + 1;
   int* nsel2 = m->counter.as<int>() + 2;
   if (n0) hipLaunchKernelGGL(k_flags_inv, dim3(blocks(n0)), dim3(256), 0, st, m->dead.as<uint8_t>(), (int)n0, m->live.as<uint8_t>());
-  MCHK(c, m->sort_tmp.reserve(std::max(prims::select_temp_bytes((int)n0), prims::select_temp_bytes((int)nin))));
-  MCHK(c, prims::select_flagged(m->sort_tmp.p, m->pts.as<float4>(), m->live.as<uint8_t>(), m->tmp.as<float4>(), nsel,
-                                (int)n0, st));
+  LISLAM_HIPCHK(c, m->sort_tmp.reserve(std::max(prims::select_temp_bytes((int)n0), prims::select_temp_bytes((int)nin))));
+  LISLAM_HIPCHK(c, prims::select_flagged(m->sort_tmp.p, m->pts.as<float4>(), m->live.as<uint8_t>(), m->tmp.as<float4>(), nsel,
+                                         (int)n0, st));
   int h[2] = {0, 0};
-  MCHK(c, hipMemcpyAsync(&h[0], nsel, sizeof(int), hipMemcpyDeviceToHost, st));
-  MCHK(c, hipStreamSynchronize(st));
-  MCHK(c, prims::select_flagged(m->sort_tmp.p, m->newp.as<float4>(), m->enter.as<uint8_t>(), m->tmp.as<float4>() + h[0],
-                                nsel2, (int)nin, st));
-  MCHK(c, hipMemcpyAsync(&h[1], nsel2, sizeof(int), hipMemcpyDeviceToHost, st));
-  MCHK(c, hipStreamSynchronize(st));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(&h[0], nsel, sizeof(int), hipMemcpyDeviceToHost, st));
+  LISLAM_HIPCHK(c, hipStreamSynchronize(st));
+  LISLAM_HIPCHK(c, prims::select_flagged(m->sort_tmp.p, m->newp.as<float4>(), m->enter.as<uint8_t>(), m->tmp.as<float4>() + h[0],
+                                         nsel2, (int)nin, st));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(&h[1], nsel2, sizeof(int), hipMemcpyDeviceToHost, st));
+  LISLAM_HIPCHK(c, hipStreamSynchronize(st));
   if (n_added) *n_added = h[1];
   return rebuild(m, (int64_t)h[0] + h[1]);
 }
@@ -1461,7 +1419,7 @@ int knn_device(lislam_map* m, const float* q, int stride, const int* qcount, int
       hipLaunchKernelGGL((k_knn<8, 64>), dim3(nb), dim3(256), 0, stream_of(c), v, q, stride, qcount, n, pose, k, max_d2,
                          out_pts, out_d2, out_found);
   }
-  MCHK(c, hipGetLastError());
+  LISLAM_HIPCHK(c, hipGetLastError());
   return LISLAM_OK;
 }
 
@@ -1470,21 +1428,21 @@ int associate_device(lislam_map* m, int match, const float* q, int stride, const
                      double* rec, int* kind) {
   lislam_ctx* c = m->ctx;
   if (n <= 0) return LISLAM_OK;
-  MCHK(c, m->sc.nb.reserve((size_t)n * 5 * sizeof(float4)));
-  MCHK(c, m->sc.d2.reserve((size_t)n * 5 * 4));
-  MCHK(c, m->sc.found.reserve((size_t)n * 4));
+  LISLAM_HIPCHK(c, m->sc.nb.reserve((size_t)n * 5 * sizeof(float4)));
+  LISLAM_HIPCHK(c, m->sc.d2.reserve((size_t)n * 5 * 4));
+  LISLAM_HIPCHK(c, m->sc.found.reserve((size_t)n * 4));
   if (m->n == 0) {
-    MCHK(c, hipMemsetAsync(m->sc.found.p, 0, (size_t)n * 4, stream_of(c)));
+    LISLAM_HIPCHK(c, hipMemsetAsync(m->sc.found.p, 0, (size_t)n * 4, stream_of(c)));
   } else {
-    MRC(knn_device(m, q, stride, qcount, n, pose, 5, 1.0f, m->sc.nb.as<float4>(), m->sc.d2.as<float>(),
-                   m->sc.found.as<int>()));
+    LISLAM_RC(knn_device(m, q, stride, qcount, n, pose, 5, 1.0f, m->sc.nb.as<float4>(), m->sc.d2.as<float>(),
+                         m->sc.found.as<int>()));
   }
   {
     TimedScope ts(c, kT_fit);
     hipLaunchKernelGGL(k_fit, dim3(blocks(n)), dim3(256), 0, stream_of(c), match, q, stride, qcount, n,
                        m->sc.nb.as<float4>(), m->sc.d2.as<float>(), m->sc.found.as<int>(), rec, kind);
   }
-  MCHK(c, hipGetLastError());
+  LISLAM_HIPCHK(c, hipGetLastError());
   return LISLAM_OK;
 }
 
@@ -1509,8 +1467,8 @@ unsigned long long map_solve_wait_ticks() {
 int solve_device(lislam_ctx* c, MapScratch& sc, const double* rec, const int* kind, const int* ncount, int n,
                  const double* x0_dev, int max_it, double* x_out, int* summary) {
   hipStream_t st = stream_of(c);
-  MCHK(c, sc.lm.reserve(sizeof(LmDev)));
-  MCHK(c, sc.partial.reserve((size_t)kMaxParts * kPart * 8 + 64));
+  LISLAM_HIPCHK(c, sc.lm.reserve(sizeof(LmDev)));
+  LISLAM_HIPCHK(c, sc.partial.reserve((size_t)kMaxParts * kPart * 8 + 64));
   LmDev* lm = sc.lm.as<LmDev>();
   unsigned* ctl = reinterpret_cast<unsigned*>(sc.partial.as<char>() + (size_t)kMaxParts * kPart * 8);
   const int parts = std::min(kMaxParts, blocks(std::max(n, 1), kEvalThreads));
@@ -1528,7 +1486,7 @@ int solve_device(lislam_ctx* c, MapScratch& sc, const double* rec, const int* ki
     hipLaunchKernelGGL(k_lm_rescue, dim3(1), dim3(kEvalThreads), 0, st, rec, kind, ncount, n, lm, sc.partial.as<double>(),
                        ctl, parts, max_it, x_out, summary);
   }
-  MCHK(c, hipGetLastError());
+  LISLAM_HIPCHK(c, hipGetLastError());
   return LISLAM_OK;
 }
 
@@ -1536,16 +1494,16 @@ int solve_device(lislam_ctx* c, MapScratch& sc, const double* rec, const int* ki
 int voxel_grid_device(lislam_ctx* c, MapScratch& sc, const float4* in, int n, float leaf, float4* out, int* n_out) {
   hipStream_t st = stream_of(c);
   if (n == 0) {
-    MCHK(c, hipMemsetAsync(n_out, 0, sizeof(int), st));
+    LISLAM_HIPCHK(c, hipMemsetAsync(n_out, 0, sizeof(int), st));
     return LISLAM_OK;
   }
-  MCHK(c, sc.bounds.reserve(64));
-  MCHK(c, sc.keys32a.reserve((size_t)n * 4));
-  MCHK(c, sc.keys32b.reserve((size_t)n * 4));
-  MCHK(c, sc.idxa.reserve((size_t)n * 4));
-  MCHK(c, sc.idxb.reserve((size_t)n * 4));
-  MCHK(c, sc.flag.reserve((size_t)n * 4));
-  MCHK(c, sc.pos.reserve((size_t)n * 4));
+  LISLAM_HIPCHK(c, sc.bounds.reserve(64));
+  LISLAM_HIPCHK(c, sc.keys32a.reserve((size_t)n * 4));
+  LISLAM_HIPCHK(c, sc.keys32b.reserve((size_t)n * 4));
+  LISLAM_HIPCHK(c, sc.idxa.reserve((size_t)n * 4));
+  LISLAM_HIPCHK(c, sc.idxb.reserve((size_t)n * 4));
+  LISLAM_HIPCHK(c, sc.flag.reserve((size_t)n * 4));
+  LISLAM_HIPCHK(c, sc.pos.reserve((size_t)n * 4));
   VgArgs a;
   a.in = in;
   a.n = n;
@@ -1554,33 +1512,33 @@ int voxel_grid_device(lislam_ctx* c, MapScratch& sc, const float4* in, int n, fl
   a.overflow = sc.bounds.as<int>() + 8;
   a.keys = sc.keys32a.as<uint32_t>();
   a.idx = sc.idxa.as<int>();
-  MCHK(c, hipMemsetAsync(a.overflow, 0, sizeof(int), st));
+  LISLAM_HIPCHK(c, hipMemsetAsync(a.overflow, 0, sizeof(int), st));
   hipLaunchKernelGGL(k_vg_bounds, dim3(1), dim3(1024), 0, st, a);
   hipLaunchKernelGGL(k_vg_keys, dim3(blocks(n)), dim3(256), 0, st, a);
-  MRC(sort_pairs_u32(c, sc.sort_tmp, sc.keys32a.as<uint32_t>(), sc.keys32b.as<uint32_t>(), sc.idxa.as<int>(),
-                     sc.idxb.as<int>(), n));
+  LISLAM_RC(sort_pairs_u32(c, sc.sort_tmp, sc.keys32a.as<uint32_t>(), sc.keys32b.as<uint32_t>(), sc.idxa.as<int>(),
+                           sc.idxb.as<int>(), n));
   hipLaunchKernelGGL(k_vg_runs, dim3(blocks(n)), dim3(256), 0, st, sc.keys32b.as<uint32_t>(), n, a.overflow, sc.flag.as<int>());
-  MCHK(c, sc.sort_tmp.reserve(prims::exclusive_sum_temp_bytes(n)));
-  MCHK(c, prims::exclusive_sum(sc.sort_tmp.p, sc.flag.as<int>(), sc.pos.as<int>(), n, st));
+  LISLAM_HIPCHK(c, sc.sort_tmp.reserve(prims::exclusive_sum_temp_bytes(n)));
+  LISLAM_HIPCHK(c, prims::exclusive_sum(sc.sort_tmp.p, sc.flag.as<int>(), sc.pos.as<int>(), n, st));
   hipLaunchKernelGGL(k_vg_centroids, dim3(blocks(n)), dim3(256), 0, st, in, sc.keys32b.as<uint32_t>(), sc.idxb.as<int>(),
                      sc.pos.as<int>(), sc.flag.as<int>(), n, a.overflow, out, n_out);
-  MCHK(c, hipGetLastError());
+  LISLAM_HIPCHK(c, hipGetLastError());
   return LISLAM_OK;
 }
 
 // host-or-device input of n points (stride floats) -> device float4 buffer (intensity = 0 when stride 3)
 int stage_points(lislam_ctx* c, MapScratch& sc, DBuf& dst, const float* pts, int n, int stride) {
   hipStream_t st = stream_of(c);
-  MCHK(c, dst.reserve((size_t)std::max(n, 1) * sizeof(float4)));
+  LISLAM_HIPCHK(c, dst.reserve((size_t)std::max(n, 1) * sizeof(float4)));
   if (n == 0) return LISLAM_OK;
   if (stride == 4) {
-    MCHK(c, hipMemcpyAsync(dst.p, pts, (size_t)n * 16, hipMemcpyDefault, st));
+    LISLAM_HIPCHK(c, hipMemcpyAsync(dst.p, pts, (size_t)n * 16, hipMemcpyDefault, st));
     return LISLAM_OK;
   }
-  MCHK(c, sc.vin.reserve((size_t)n * stride * 4));
-  MCHK(c, hipMemcpyAsync(sc.vin.p, pts, (size_t)n * stride * 4, hipMemcpyDefault, st));
+  LISLAM_HIPCHK(c, sc.vin.reserve((size_t)n * stride * 4));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(sc.vin.p, pts, (size_t)n * stride * 4, hipMemcpyDefault, st));
   hipLaunchKernelGGL(k_pack_points, dim3(blocks(n)), dim3(256), 0, st, sc.vin.as<float>(), n, stride, 0, dst.as<float4>());
-  MCHK(c, hipGetLastError());
+  LISLAM_HIPCHK(c, hipGetLastError());
   return LISLAM_OK;
 }
 
@@ -1599,7 +1557,7 @@ extern "C" {
 int lislam_map_create(lislam_ctx* c, const lislam_map_config* cfg, lislam_map** out) {
   if (!c || !cfg || !out) return LISLAM_ERR_ARG;
   *out = nullptr;
-  if (!(cfg->downsample_size > 0) || cfg->cell_size < 0) return mfail(c, LISLAM_ERR_ARG, "lislam_map_create: bad sizes");
+  if (!(cfg->downsample_size > 0) || cfg->cell_size < 0) return fail(c, LISLAM_ERR_ARG, "lislam_map_create: bad sizes");
   hipSetDevice(c->device);
   lislam_map* m = new lislam_map();
   m->ctx = c;
@@ -1618,11 +1576,11 @@ int lislam_map_set_timing(lislam_ctx* c, int32_t enable) {
 int lislam_map_kernel_times(lislam_ctx* c, float* ms, int32_t* launches) {
   if (!c || !ms) return LISLAM_ERR_ARG;
   hipSetDevice(c->device);
-  MCHK(c, hipStreamSynchronize(c->stream));
+  LISLAM_HIPCHK(c, hipStreamSynchronize(c->stream));
   for (int k = 0; k < kT_count; k++) { ms[k] = 0; if (launches) launches[k] = 0; }
   for (auto& r : c->mtimer.rec) {
     float t = 0;
-    MCHK(c, hipEventElapsedTime(&t, r.second.first, r.second.second));
+    LISLAM_HIPCHK(c, hipEventElapsedTime(&t, r.second.first, r.second.second));
     lislam::timeline_print(c->device, "ctx", c, r.first, r.second.first, r.second.second);
     ms[r.first] += t;
     if (launches) launches[r.first]++;
@@ -1644,26 +1602,26 @@ int lislam_map_destroy(lislam_map* m) {
 int lislam_map_build(lislam_map* m, const float* pts, int64_t n, int32_t stride) {
   if (!m || n < 0 || (n > 0 && !pts) || !valid_stride(stride) || n > 0x7fffffff) return LISLAM_ERR_ARG;
   hipSetDevice(m->ctx->device);
-  MCHK(m->ctx, m->tmp.reserve((size_t)std::max<int64_t>(n, 1) * sizeof(float4)));
-  MRC(upload_points(m, pts, n, stride, 0, m->tmp, 0));
+  LISLAM_HIPCHK(m->ctx, m->tmp.reserve((size_t)std::max<int64_t>(n, 1) * sizeof(float4)));
+  LISLAM_RC(upload_points(m, pts, n, stride, 0, m->tmp, 0));
   m->next_id = (int)n;
-  MRC(rebuild(m, n));
-  MCHK(m->ctx, hipStreamSynchronize(m->ctx->stream));
+  LISLAM_RC(rebuild(m, n));
+  LISLAM_HIPCHK(m->ctx, hipStreamSynchronize(m->ctx->stream));
   return LISLAM_OK;
 }
 
 int lislam_map_add_points(lislam_map* m, const float* pts, int64_t n, int32_t stride, int32_t downsample_on,
                           int64_t* n_added) {
   if (!m || n < 0 || (n > 0 && !pts) || !valid_stride(stride)) return LISLAM_ERR_ARG;
-  if (m->n + n > 0x7fffffff || (int64_t)m->next_id + n > 0x7fffffff) return mfail(m->ctx, LISLAM_ERR_CAPACITY, "map too large");
+  if (m->n + n > 0x7fffffff || (int64_t)m->next_id + n > 0x7fffffff) return fail(m->ctx, LISLAM_ERR_CAPACITY, "map too large");
   hipSetDevice(m->ctx->device);
   if (n_added) *n_added = 0;
   if (n == 0) return LISLAM_OK;
-  MCHK(m->ctx, m->newp.reserve((size_t)n * sizeof(float4)));
-  MRC(upload_points(m, pts, n, stride, m->next_id, m->newp, 0));
+  LISLAM_HIPCHK(m->ctx, m->newp.reserve((size_t)n * sizeof(float4)));
+  LISLAM_RC(upload_points(m, pts, n, stride, m->next_id, m->newp, 0));
   m->next_id += (int)n;
-  MRC(add_packed(m, n, downsample_on != 0, n_added));
-  MCHK(m->ctx, hipStreamSynchronize(m->ctx->stream));
+  LISLAM_RC(add_packed(m, n, downsample_on != 0, n_added));
+  LISLAM_HIPCHK(m->ctx, hipStreamSynchronize(m->ctx->stream));
   return LISLAM_OK;
 }
 
@@ -1677,11 +1635,11 @@ int lislam_map_points(lislam_map* m, float* out, int64_t cap, int64_t* n) {
   if (!m || !n) return LISLAM_ERR_ARG;
   *n = m->n;
   if (m->n == 0) return LISLAM_OK;
-  if (!out || cap < m->n) return mfail(m->ctx, LISLAM_ERR_CAPACITY, "lislam_map_points: capacity %lld < %lld",
-                                       (long long)cap, (long long)m->n);
+  if (!out || cap < m->n) return fail(m->ctx, LISLAM_ERR_CAPACITY, "lislam_map_points: capacity %lld < %lld",
+                                      (long long)cap, (long long)m->n);
   hipSetDevice(m->ctx->device);
-  MCHK(m->ctx, hipMemcpyAsync(out, m->pts.p, m->n * sizeof(float4), hipMemcpyDefault, m->ctx->stream));
-  MCHK(m->ctx, hipStreamSynchronize(m->ctx->stream));
+  LISLAM_HIPCHK(m->ctx, hipMemcpyAsync(out, m->pts.p, m->n * sizeof(float4), hipMemcpyDefault, m->ctx->stream));
+  LISLAM_HIPCHK(m->ctx, hipStreamSynchronize(m->ctx->stream));
   return LISLAM_OK;
 }
 
@@ -1693,26 +1651,26 @@ int lislam_map_nearest_search(lislam_map* m, const float* queries, int32_t n, in
   hipSetDevice(c->device);
   MapScratch& sc = m->sc;
   hipStream_t st = stream_of(c);
-  MCHK(c, sc.q.reserve((size_t)n * stride * 4));
-  MCHK(c, hipMemcpyAsync(sc.q.p, queries, (size_t)n * stride * 4, hipMemcpyDefault, st));
-  MCHK(c, sc.nb.reserve((size_t)n * k * sizeof(float4)));
-  MCHK(c, sc.d2.reserve((size_t)n * k * 4));
-  MCHK(c, sc.found.reserve((size_t)n * 4));
+  LISLAM_HIPCHK(c, sc.q.reserve((size_t)n * stride * 4));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(sc.q.p, queries, (size_t)n * stride * 4, hipMemcpyDefault, st));
+  LISLAM_HIPCHK(c, sc.nb.reserve((size_t)n * k * sizeof(float4)));
+  LISLAM_HIPCHK(c, sc.d2.reserve((size_t)n * k * 4));
+  LISLAM_HIPCHK(c, sc.found.reserve((size_t)n * 4));
   const float md2 = max_dist > 0 ? max_dist * max_dist : kInf;
   if (m->n == 0) {
-    MCHK(c, hipMemsetAsync(sc.nb.p, 0, (size_t)n * k * sizeof(float4), st));
+    LISLAM_HIPCHK(c, hipMemsetAsync(sc.nb.p, 0, (size_t)n * k * sizeof(float4), st));
     std::vector<float> inf((size_t)n * k, kInf);
-    MCHK(c, hipMemcpyAsync(sc.d2.p, inf.data(), inf.size() * 4, hipMemcpyHostToDevice, st));
-    MCHK(c, hipMemsetAsync(sc.found.p, 0, (size_t)n * 4, st));
-    MCHK(c, hipStreamSynchronize(st));
+    LISLAM_HIPCHK(c, hipMemcpyAsync(sc.d2.p, inf.data(), inf.size() * 4, hipMemcpyHostToDevice, st));
+    LISLAM_HIPCHK(c, hipMemsetAsync(sc.found.p, 0, (size_t)n * 4, st));
+    LISLAM_HIPCHK(c, hipStreamSynchronize(st));
   } else {
-    MRC(knn_device(m, sc.q.as<float>(), stride, nullptr, n, nullptr, k, md2, sc.nb.as<float4>(), sc.d2.as<float>(),
-                   sc.found.as<int>()));
+    LISLAM_RC(knn_device(m, sc.q.as<float>(), stride, nullptr, n, nullptr, k, md2, sc.nb.as<float4>(), sc.d2.as<float>(),
+                         sc.found.as<int>()));
   }
-  if (out_pts) MCHK(c, hipMemcpyAsync(out_pts, sc.nb.p, (size_t)n * k * sizeof(float4), hipMemcpyDefault, st));
-  if (out_d2) MCHK(c, hipMemcpyAsync(out_d2, sc.d2.p, (size_t)n * k * 4, hipMemcpyDefault, st));
-  if (out_found) MCHK(c, hipMemcpyAsync(out_found, sc.found.p, (size_t)n * 4, hipMemcpyDefault, st));
-  MCHK(c, hipStreamSynchronize(st));
+  if (out_pts) LISLAM_HIPCHK(c, hipMemcpyAsync(out_pts, sc.nb.p, (size_t)n * k * sizeof(float4), hipMemcpyDefault, st));
+  if (out_d2) LISLAM_HIPCHK(c, hipMemcpyAsync(out_d2, sc.d2.p, (size_t)n * k * 4, hipMemcpyDefault, st));
+  if (out_found) LISLAM_HIPCHK(c, hipMemcpyAsync(out_found, sc.found.p, (size_t)n * 4, hipMemcpyDefault, st));
+  LISLAM_HIPCHK(c, hipStreamSynchronize(st));
   return LISLAM_OK;
 }
 
@@ -1724,17 +1682,17 @@ int lislam_map_associate(lislam_map* m, int32_t kind, const float* pts, int32_t 
   hipSetDevice(c->device);
   MapScratch& sc = m->sc;
   hipStream_t st = stream_of(c);
-  MCHK(c, sc.q.reserve((size_t)n * stride * 4));
-  MCHK(c, hipMemcpyAsync(sc.q.p, pts, (size_t)n * stride * 4, hipMemcpyDefault, st));
-  MCHK(c, sc.x.reserve(64));
-  MCHK(c, hipMemcpyAsync(sc.x.p, x, 56, hipMemcpyDefault, st));
-  MCHK(c, sc.rec.reserve((size_t)n * 72));
-  MCHK(c, sc.kind.reserve((size_t)n * 4));
-  MRC(associate_device(m, kind, sc.q.as<float>(), stride, nullptr, n, sc.x.as<double>(), sc.rec.as<double>(),
-                       sc.kind.as<int>()));
-  if (out_rec) MCHK(c, hipMemcpyAsync(out_rec, sc.rec.p, (size_t)n * 72, hipMemcpyDefault, st));
-  if (out_kind) MCHK(c, hipMemcpyAsync(out_kind, sc.kind.p, (size_t)n * 4, hipMemcpyDefault, st));
-  MCHK(c, hipStreamSynchronize(st));
+  LISLAM_HIPCHK(c, sc.q.reserve((size_t)n * stride * 4));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(sc.q.p, pts, (size_t)n * stride * 4, hipMemcpyDefault, st));
+  LISLAM_HIPCHK(c, sc.x.reserve(64));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(sc.x.p, x, 56, hipMemcpyDefault, st));
+  LISLAM_HIPCHK(c, sc.rec.reserve((size_t)n * 72));
+  LISLAM_HIPCHK(c, sc.kind.reserve((size_t)n * 4));
+  LISLAM_RC(associate_device(m, kind, sc.q.as<float>(), stride, nullptr, n, sc.x.as<double>(), sc.rec.as<double>(),
+                             sc.kind.as<int>()));
+  if (out_rec) LISLAM_HIPCHK(c, hipMemcpyAsync(out_rec, sc.rec.p, (size_t)n * 72, hipMemcpyDefault, st));
+  if (out_kind) LISLAM_HIPCHK(c, hipMemcpyAsync(out_kind, sc.kind.p, (size_t)n * 4, hipMemcpyDefault, st));
+  LISLAM_HIPCHK(c, hipStreamSynchronize(st));
   return LISLAM_OK;
 }
 
@@ -1744,24 +1702,24 @@ int lislam_normal_equations(lislam_ctx* c, const double* rec, const int32_t* kin
   hipSetDevice(c->device);
   MapScratch& sc = ctx_scratch(c);
   hipStream_t st = stream_of(c);
-  MCHK(c, sc.rec.reserve((size_t)std::max(n, 1) * 72));
-  MCHK(c, sc.kind.reserve((size_t)std::max(n, 1) * 4));
-  MCHK(c, sc.lm.reserve(sizeof(LmDev)));
-  MCHK(c, sc.partial.reserve((size_t)kMaxParts * kPart * 8));
-  MCHK(c, sc.x.reserve(64));
+  LISLAM_HIPCHK(c, sc.rec.reserve((size_t)std::max(n, 1) * 72));
+  LISLAM_HIPCHK(c, sc.kind.reserve((size_t)std::max(n, 1) * 4));
+  LISLAM_HIPCHK(c, sc.lm.reserve(sizeof(LmDev)));
+  LISLAM_HIPCHK(c, sc.partial.reserve((size_t)kMaxParts * kPart * 8));
+  LISLAM_HIPCHK(c, sc.x.reserve(64));
   if (n) {
-    MCHK(c, hipMemcpyAsync(sc.rec.p, rec, (size_t)n * 72, hipMemcpyDefault, st));
-    MCHK(c, hipMemcpyAsync(sc.kind.p, kind, (size_t)n * 4, hipMemcpyDefault, st));
+    LISLAM_HIPCHK(c, hipMemcpyAsync(sc.rec.p, rec, (size_t)n * 72, hipMemcpyDefault, st));
+    LISLAM_HIPCHK(c, hipMemcpyAsync(sc.kind.p, kind, (size_t)n * 4, hipMemcpyDefault, st));
   }
-  MCHK(c, hipMemcpyAsync(sc.x.p, x, 56, hipMemcpyDefault, st));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(sc.x.p, x, 56, hipMemcpyDefault, st));
   LmDev* lm = sc.lm.as<LmDev>();
   hipLaunchKernelGGL(k_lm_init, dim3(1), dim3(64), 0, st, lm, sc.x.as<double>(), (unsigned*)nullptr);
   const int parts = std::min(kMaxParts, blocks(std::max(n, 1), kEvalThreads));
   hipLaunchKernelGGL(k_lm_eval, dim3(parts), dim3(kEvalThreads), 0, st, sc.rec.as<double>(), sc.kind.as<int>(), nullptr,
                      n, lm, sc.partial.as<double>());
   std::vector<double> part((size_t)parts * kPart);
-  MCHK(c, hipMemcpyAsync(part.data(), sc.partial.p, part.size() * 8, hipMemcpyDeviceToHost, st));
-  MCHK(c, hipStreamSynchronize(st));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(part.data(), sc.partial.p, part.size() * 8, hipMemcpyDeviceToHost, st));
+  LISLAM_HIPCHK(c, hipStreamSynchronize(st));
   for (int e = 0; e < kAcc; e++) {
     double v = 0;
     for (int p = 0; p < parts; p++) v += part[(size_t)p * kPart + e];
@@ -1776,21 +1734,21 @@ int lislam_pose_solve(lislam_ctx* c, const double* rec, const int32_t* kind, int
   hipSetDevice(c->device);
   MapScratch& sc = ctx_scratch(c);
   hipStream_t st = stream_of(c);
-  MCHK(c, sc.rec.reserve((size_t)std::max(n, 1) * 72));
-  MCHK(c, sc.kind.reserve((size_t)std::max(n, 1) * 4));
-  MCHK(c, sc.x.reserve(128));
+  LISLAM_HIPCHK(c, sc.rec.reserve((size_t)std::max(n, 1) * 72));
+  LISLAM_HIPCHK(c, sc.kind.reserve((size_t)std::max(n, 1) * 4));
+  LISLAM_HIPCHK(c, sc.x.reserve(128));
   if (n) {
-    MCHK(c, hipMemcpyAsync(sc.rec.p, rec, (size_t)n * 72, hipMemcpyDefault, st));
-    MCHK(c, hipMemcpyAsync(sc.kind.p, kind, (size_t)n * 4, hipMemcpyDefault, st));
+    LISLAM_HIPCHK(c, hipMemcpyAsync(sc.rec.p, rec, (size_t)n * 72, hipMemcpyDefault, st));
+    LISLAM_HIPCHK(c, hipMemcpyAsync(sc.kind.p, kind, (size_t)n * 4, hipMemcpyDefault, st));
   }
-  MCHK(c, hipMemcpyAsync(sc.x.p, x, 56, hipMemcpyDefault, st));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(sc.x.p, x, 56, hipMemcpyDefault, st));
   int* dsum = reinterpret_cast<int*>(sc.x.as<double>() + 8);
-  MRC(solve_device(c, sc, sc.rec.as<double>(), sc.kind.as<int>(), nullptr, n, sc.x.as<double>(), max_iterations,
-                   sc.x.as<double>(), dsum));
+  LISLAM_RC(solve_device(c, sc, sc.rec.as<double>(), sc.kind.as<int>(), nullptr, n, sc.x.as<double>(), max_iterations,
+                         sc.x.as<double>(), dsum));
   int hs[4];
-  MCHK(c, hipMemcpyAsync(x, sc.x.p, 56, hipMemcpyDefault, st));
-  MCHK(c, hipMemcpyAsync(hs, dsum, 16, hipMemcpyDeviceToHost, st));
-  MCHK(c, hipStreamSynchronize(st));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(x, sc.x.p, 56, hipMemcpyDefault, st));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(hs, dsum, 16, hipMemcpyDeviceToHost, st));
+  LISLAM_HIPCHK(c, hipStreamSynchronize(st));
   if (summary) for (int e = 0; e < 4; e++) summary[e] = hs[e];
   return LISLAM_OK;
 }
@@ -1800,15 +1758,15 @@ int lislam_voxel_grid(lislam_ctx* c, const float* pts, int32_t n, float leaf, fl
   hipSetDevice(c->device);
   MapScratch& sc = ctx_scratch(c);
   hipStream_t st = stream_of(c);
-  MRC(stage_points(c, sc, sc.q, pts, n, 4));
-  MCHK(c, sc.vout.reserve((size_t)std::max(n, 1) * 16));
-  MCHK(c, sc.counters.reserve(64));
-  MRC(voxel_grid_device(c, sc, sc.q.as<float4>(), n, leaf, sc.vout.as<float4>(), sc.counters.as<int>()));
+  LISLAM_RC(stage_points(c, sc, sc.q, pts, n, 4));
+  LISLAM_HIPCHK(c, sc.vout.reserve((size_t)std::max(n, 1) * 16));
+  LISLAM_HIPCHK(c, sc.counters.reserve(64));
+  LISLAM_RC(voxel_grid_device(c, sc, sc.q.as<float4>(), n, leaf, sc.vout.as<float4>(), sc.counters.as<int>()));
   int no = 0;
-  MCHK(c, hipMemcpyAsync(&no, sc.counters.p, 4, hipMemcpyDeviceToHost, st));
-  MCHK(c, hipStreamSynchronize(st));
-  if (no) MCHK(c, hipMemcpyAsync(out, sc.vout.p, (size_t)no * 16, hipMemcpyDefault, st));
-  MCHK(c, hipStreamSynchronize(st));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(&no, sc.counters.p, 4, hipMemcpyDeviceToHost, st));
+  LISLAM_HIPCHK(c, hipStreamSynchronize(st));
+  if (no) LISLAM_HIPCHK(c, hipMemcpyAsync(out, sc.vout.p, (size_t)no * 16, hipMemcpyDefault, st));
+  LISLAM_HIPCHK(c, hipStreamSynchronize(st));
   *n_out = no;
   return LISLAM_OK;
 }
@@ -1825,23 +1783,23 @@ static int corner_map_update(lislam_map* cm, const float* corner, int nc, const 
   lislam_ctx* c = cm->ctx;
   hipStream_t st = stream_of(c);
   MapScratch& sc = cm->sc;
-  MRC(stage_points(c, sc, sc.vout, corner, nc, 4));
-  MCHK(c, sc.vin.reserve((size_t)std::max(nc, 1) * 16));
+  LISLAM_RC(stage_points(c, sc, sc.vout, corner, nc, 4));
+  LISLAM_HIPCHK(c, sc.vin.reserve((size_t)std::max(nc, 1) * 16));
   hipLaunchKernelGGL(k_transform, dim3(blocks(nc)), dim3(256), 0, st, sc.vout.as<float>(), 4, (const int*)nullptr, nc,
                      pose, sc.vin.as<float>());
   if (first) {
-    MCHK(c, cm->tmp.reserve((size_t)std::max(nc, 1) * 16));
+    LISLAM_HIPCHK(c, cm->tmp.reserve((size_t)std::max(nc, 1) * 16));
     hipLaunchKernelGGL(k_pack_points, dim3(blocks(nc)), dim3(256), 0, st, sc.vin.as<float>(), nc, 4, 0, cm->tmp.as<float4>());
     cm->next_id = nc;
-    MRC(rebuild(cm, nc));
+    LISLAM_RC(rebuild(cm, nc));
   } else {
-    MCHK(c, cm->newp.reserve((size_t)std::max(nc, 1) * 16));
+    LISLAM_HIPCHK(c, cm->newp.reserve((size_t)std::max(nc, 1) * 16));
     hipLaunchKernelGGL(k_pack_points, dim3(blocks(nc)), dim3(256), 0, st, sc.vin.as<float>(), nc, 4, cm->next_id,
                        cm->newp.as<float4>());
     cm->next_id += nc;
-    MRC(add_packed(cm, nc, true, nullptr));
+    LISLAM_RC(add_packed(cm, nc, true, nullptr));
   }
-  MCHK(c, hipGetLastError());
+  LISLAM_HIPCHK(c, hipGetLastError());
   return LISLAM_OK;
 }
 
@@ -1858,50 +1816,50 @@ static int mapopt_step_impl(lislam_map* m, lislam_map* cm, lislam_mapwin* win, c
   hipSetDevice(c->device);
   MapScratch& sc = m->sc;
   hipStream_t st = stream_of(c);
-  if (win) MRC(mapwin::stage(win, desc, p3d, nf));  // before anything changes: too many features change nothing
+  if (win) LISLAM_RC(mapwin::stage(win, desc, p3d, nf));  // before anything changes: too many features change nothing
   int hwin[mapwin::kMaxWindow * 6 + 2] = {};
   int nwin = 0;
   // device pose block: [0,7) state, [8,15) odom, [16,23) x, [24,31) keyframe pose
-  MCHK(c, sc.x.reserve(40 * 8));
+  LISLAM_HIPCHK(c, sc.x.reserve(40 * 8));
   double* dp = sc.x.as<double>();
-  MCHK(c, hipMemcpyAsync(dp, state, 56, hipMemcpyDefault, st));
-  MCHK(c, hipMemcpyAsync(dp + 8, odom, 56, hipMemcpyDefault, st));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(dp, state, 56, hipMemcpyDefault, st));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(dp + 8, odom, 56, hipMemcpyDefault, st));
   hipLaunchKernelGGL(k_mapopt_pose, dim3(1), dim3(64), 0, st, 0, dp, dp + 8, dp + 16, (const LmDev*)nullptr, dp + 24);
   int32_t summ[5] = {0, 0, -1, 0, 0};
-  MRC(stage_points(c, sc, sc.vout, ground, n, 4));  // sensor-frame ground cloud (float4)
+  LISLAM_RC(stage_points(c, sc, sc.vout, ground, n, 4));  // sensor-frame ground cloud (float4)
   if (m->n == 0) {  // first keyframe: Build with the transformed raw cloud (mapOptimization.cpp:185-192)
-    MCHK(c, m->tmp.reserve((size_t)std::max(n, 1) * 16));
-    MCHK(c, sc.vin.reserve((size_t)std::max(n, 1) * 16));
+    LISLAM_HIPCHK(c, m->tmp.reserve((size_t)std::max(n, 1) * 16));
+    LISLAM_HIPCHK(c, sc.vin.reserve((size_t)std::max(n, 1) * 16));
     hipLaunchKernelGGL(k_transform, dim3(blocks(n)), dim3(256), 0, st, sc.vout.as<float>(), 4, (const int*)nullptr, n,
                        dp + 16, sc.vin.as<float>());
     hipLaunchKernelGGL(k_pack_points, dim3(blocks(n)), dim3(256), 0, st, sc.vin.as<float>(), n, 4, 0, m->tmp.as<float4>());
     m->next_id = n;
-    MRC(rebuild(m, n));
-    if (cm && nc > 0) MRC(corner_map_update(cm, corner, nc, dp + 16, true));
-    MCHK(c, hipMemcpyAsync(out_pose, dp + 16, 56, hipMemcpyDefault, st));
+    LISLAM_RC(rebuild(m, n));
+    if (cm && nc > 0) LISLAM_RC(corner_map_update(cm, corner, nc, dp + 16, true));
+    LISLAM_HIPCHK(c, hipMemcpyAsync(out_pose, dp + 16, 56, hipMemcpyDefault, st));
   } else {
     // VoxelGrid(0.8) (:368-370) of the xyz cloud (PointXYZ: intensity lane zeroed)
-    MCHK(c, sc.flag.reserve((size_t)std::max(n, 1) * 4));
-    MCHK(c, sc.counters.reserve(64));
-    MCHK(c, sc.vin.reserve((size_t)std::max(n, 1) * 16));
-    MCHK(c, hipMemcpy2DAsync(sc.vin.p, 16, sc.vout.p, 16, 12, n, hipMemcpyDeviceToDevice, st));
-    MCHK(c, hipMemset2DAsync(sc.vin.as<char>() + 12, 16, 0, 4, n, st));
+    LISLAM_HIPCHK(c, sc.flag.reserve((size_t)std::max(n, 1) * 4));
+    LISLAM_HIPCHK(c, sc.counters.reserve(64));
+    LISLAM_HIPCHK(c, sc.vin.reserve((size_t)std::max(n, 1) * 16));
+    LISLAM_HIPCHK(c, hipMemcpy2DAsync(sc.vin.p, 16, sc.vout.p, 16, 12, n, hipMemcpyDeviceToDevice, st));
+    LISLAM_HIPCHK(c, hipMemset2DAsync(sc.vin.as<char>() + 12, 16, 0, 4, n, st));
     DBuf& voxbuf = sc.vox;
-    MCHK(c, voxbuf.reserve((size_t)std::max(n, 1) * 16));
+    LISLAM_HIPCHK(c, voxbuf.reserve((size_t)std::max(n, 1) * 16));
     int* nvox = sc.counters.as<int>();
-    MRC(voxel_grid_device(c, sc, sc.vin.as<float4>(), n, 0.8f, voxbuf.as<float4>(), nvox));
-    MCHK(c, sc.rec.reserve((size_t)std::max(n, 1) * 72));
-    MCHK(c, sc.kind.reserve((size_t)std::max(n, 1) * 4));
-    MRC(associate_device(m, 1, voxbuf.as<float>(), 4, nvox, n, dp + 16, sc.rec.as<double>(), sc.kind.as<int>()));
+    LISLAM_RC(voxel_grid_device(c, sc, sc.vin.as<float4>(), n, 0.8f, voxbuf.as<float4>(), nvox));
+    LISLAM_HIPCHK(c, sc.rec.reserve((size_t)std::max(n, 1) * 72));
+    LISLAM_HIPCHK(c, sc.kind.reserve((size_t)std::max(n, 1) * 4));
+    LISLAM_RC(associate_device(m, 1, voxbuf.as<float>(), 4, nvox, n, dp + 16, sc.rec.as<double>(), sc.kind.as<int>()));
     if (win) {
       // mapOptimization.cpp:295-361 at the initial guess, then the planes behind the feature
       // blocks: one problem, one loss (:233, :354, :424)
-      MRC(mapwin::records(win, dp + 16, n));
-      MRC(mapwin::append(win, sc.rec.as<double>(), sc.kind.as<int>(), nvox, n));
-      MRC(solve_device(c, sc, mapwin::rec(win), mapwin::kind(win), mapwin::total(win), mapwin::capacity_records(win) + n,
-                       dp + 16, 10, nullptr, nullptr));
+      LISLAM_RC(mapwin::records(win, dp + 16, n));
+      LISLAM_RC(mapwin::append(win, sc.rec.as<double>(), sc.kind.as<int>(), nvox, n));
+      LISLAM_RC(solve_device(c, sc, mapwin::rec(win), mapwin::kind(win), mapwin::total(win), mapwin::capacity_records(win) + n,
+                             dp + 16, 10, nullptr, nullptr));
     } else {
-      MRC(solve_device(c, sc, sc.rec.as<double>(), sc.kind.as<int>(), nvox, n, dp + 16, 10, nullptr, nullptr));
+      LISLAM_RC(solve_device(c, sc, sc.rec.as<double>(), sc.kind.as<int>(), nvox, n, dp + 16, 10, nullptr, nullptr));
     }
     LmDev* lm = sc.lm.as<LmDev>();
     hipLaunchKernelGGL(k_mapopt_pose, dim3(1), dim3(64), 0, st, 1, dp, dp + 8, dp + 16, lm, dp + 24);
@@ -1911,18 +1869,18 @@ static int mapopt_step_impl(lislam_map* m, lislam_map* cm, lislam_mapwin* win, c
       // :481-493: the keyframe enters the window with the optimised pose on CONVERGENCE, else
       // with the initial guess — the keyframe pose k_mapopt_pose selected
       (void)lislam_mapwin_size(win, &nwin);
-      MCHK(c, hipMemcpyAsync(hwin, mapwin::info(win), sizeof(hwin), hipMemcpyDeviceToHost, st));
-      MRC(mapwin::push_staged(win, dp + 24));
+      LISLAM_HIPCHK(c, hipMemcpyAsync(hwin, mapwin::info(win), sizeof(hwin), hipMemcpyDeviceToHost, st));
+      LISLAM_RC(mapwin::push_staged(win, dp + 24));
     }
     // Add_Points(downsample) of the voxelized cloud at the keyframe pose (:467-475)
-    MCHK(c, m->newp.reserve((size_t)std::max(n, 1) * 16));
+    LISLAM_HIPCHK(c, m->newp.reserve((size_t)std::max(n, 1) * 16));
     hipLaunchKernelGGL(k_transform, dim3(blocks(n)), dim3(256), 0, st, voxbuf.as<float>(), 4, nvox, n, dp + 24,
                        sc.vin.as<float>());
     int hn = 0;
     int hs[4];
-    MCHK(c, hipMemcpyAsync(&hn, nvox, 4, hipMemcpyDeviceToHost, st));
-    MCHK(c, hipMemcpyAsync(hs, dsum, 16, hipMemcpyDeviceToHost, st));
-    MCHK(c, hipStreamSynchronize(st));
+    LISLAM_HIPCHK(c, hipMemcpyAsync(&hn, nvox, 4, hipMemcpyDeviceToHost, st));
+    LISLAM_HIPCHK(c, hipMemcpyAsync(hs, dsum, 16, hipMemcpyDeviceToHost, st));
+    LISLAM_HIPCHK(c, hipStreamSynchronize(st));
     summ[3] = hwin[nwin * 6];  // kind-3 blocks count with the planes in the solve's summary
     summ[4] = hwin[nwin * 6 + 1];
     summ[0] = hs[3] - summ[3];
@@ -1931,12 +1889,12 @@ static int mapopt_step_impl(lislam_map* m, lislam_map* cm, lislam_mapwin* win, c
     hipLaunchKernelGGL(k_pack_points, dim3(blocks(hn)), dim3(256), 0, st, sc.vin.as<float>(), hn, 4, m->next_id,
                        m->newp.as<float4>());
     m->next_id += hn;
-    MRC(add_packed(m, hn, true, nullptr));
-    if (cm && nc > 0) MRC(corner_map_update(cm, corner, nc, dp + 24, false));  // the same keyframe pose as the ground cloud
-    MCHK(c, hipMemcpyAsync(out_pose, dp + 16, 56, hipMemcpyDefault, st));
-    MCHK(c, hipMemcpyAsync(state, dp, 56, hipMemcpyDefault, st));
+    LISLAM_RC(add_packed(m, hn, true, nullptr));
+    if (cm && nc > 0) LISLAM_RC(corner_map_update(cm, corner, nc, dp + 24, false));  // the same keyframe pose as the ground cloud
+    LISLAM_HIPCHK(c, hipMemcpyAsync(out_pose, dp + 16, 56, hipMemcpyDefault, st));
+    LISLAM_HIPCHK(c, hipMemcpyAsync(state, dp, 56, hipMemcpyDefault, st));
   }
-  MCHK(c, hipStreamSynchronize(st));
+  LISLAM_HIPCHK(c, hipStreamSynchronize(st));
   if (summary) for (int e = 0; e < nsum; e++) summary[e] = summ[e];
   return LISLAM_OK;
 }
@@ -1952,8 +1910,8 @@ int lislam_mapopt_step_window(lislam_map* m, lislam_map* cm, lislam_mapwin* win,
   if (win && (!m || mapwin::context(win) != m->ctx)) return LISLAM_ERR_ARG;
   if (win && (nf < 0 || (nf > 0 && (!desc || !p3d)))) return LISLAM_ERR_ARG;
   if (win && nf > mapwin::feature_capacity(win))
-    return mfail(m->ctx, LISLAM_ERR_CAPACITY, "lislam_mapopt_step_window: %d features > feature_capacity %d", nf,
-                 mapwin::feature_capacity(win));
+    return fail(m->ctx, LISLAM_ERR_CAPACITY, "lislam_mapopt_step_window: %d features > feature_capacity %d", nf,
+                mapwin::feature_capacity(win));
   if (win && mapwin::window_size(win) == 0) win = nullptr;  // the window pops what it pushes (:491-493)
   return mapopt_step_impl(m, cm, win, ground, n, corner, nc, desc, p3d, nf, odom, state, out_pose, summary, 5);
 }
@@ -1967,26 +1925,26 @@ int lislam_laser_mapping(lislam_map* mc, lislam_map* ms, const float* corner, in
   MapScratch& sc = mc->sc;
   hipStream_t st = stream_of(c);
   const int n = nc + ns;
-  MCHK(c, sc.x.reserve(40 * 8));
+  LISLAM_HIPCHK(c, sc.x.reserve(40 * 8));
   double* dp = sc.x.as<double>();
-  MCHK(c, hipMemcpyAsync(dp, x, 56, hipMemcpyDefault, st));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(dp, x, 56, hipMemcpyDefault, st));
   DBuf& qc = sc.qc;
   DBuf& qs = sc.qs;
-  MRC(stage_points(c, sc, qc, corner, nc, 4));
-  MRC(stage_points(c, sc, qs, surf, ns, 4));
-  MCHK(c, sc.rec.reserve((size_t)std::max(n, 1) * 72));
-  MCHK(c, sc.kind.reserve((size_t)std::max(n, 1) * 4));
+  LISLAM_RC(stage_points(c, sc, qc, corner, nc, 4));
+  LISLAM_RC(stage_points(c, sc, qs, surf, ns, 4));
+  LISLAM_HIPCHK(c, sc.rec.reserve((size_t)std::max(n, 1) * 72));
+  LISLAM_HIPCHK(c, sc.kind.reserve((size_t)std::max(n, 1) * 4));
   int hs[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
   int* dsum = reinterpret_cast<int*>(dp + 32);
   for (int outer = 0; outer < 2; outer++) {
-    MRC(associate_device(mc, 0, qc.as<float>(), 4, nullptr, nc, dp, sc.rec.as<double>(), sc.kind.as<int>()));
-    MRC(associate_device(ms, 1, qs.as<float>(), 4, nullptr, ns, dp, sc.rec.as<double>() + (size_t)nc * 9,
-                         sc.kind.as<int>() + nc));
-    MRC(solve_device(c, sc, sc.rec.as<double>(), sc.kind.as<int>(), nullptr, n, dp, 4, dp, dsum + outer * 4));
+    LISLAM_RC(associate_device(mc, 0, qc.as<float>(), 4, nullptr, nc, dp, sc.rec.as<double>(), sc.kind.as<int>()));
+    LISLAM_RC(associate_device(ms, 1, qs.as<float>(), 4, nullptr, ns, dp, sc.rec.as<double>() + (size_t)nc * 9,
+                               sc.kind.as<int>() + nc));
+    LISLAM_RC(solve_device(c, sc, sc.rec.as<double>(), sc.kind.as<int>(), nullptr, n, dp, 4, dp, dsum + outer * 4));
   }
-  MCHK(c, hipMemcpyAsync(x, dp, 56, hipMemcpyDefault, st));
-  MCHK(c, hipMemcpyAsync(hs, dsum, 32, hipMemcpyDeviceToHost, st));
-  MCHK(c, hipStreamSynchronize(st));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(x, dp, 56, hipMemcpyDefault, st));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(hs, dsum, 32, hipMemcpyDeviceToHost, st));
+  LISLAM_HIPCHK(c, hipStreamSynchronize(st));
   if (stats)
     for (int o = 0; o < 2; o++) { stats[o * 2] = hs[o][2]; stats[o * 2 + 1] = hs[o][3]; }
   return LISLAM_OK;
@@ -2216,10 +2174,10 @@ using namespace lislam::cubek;
 // offsets of pool w after its points / cubes changed (n on the host)
 int cm_offsets(lislam_lmap* L, int w) {
   lislam_ctx* c = L->ctx;
-  MCHK(c, L->off[w].reserve((kNC + 1) * sizeof(int)));
+  LISLAM_HIPCHK(c, L->off[w].reserve((kNC + 1) * sizeof(int)));
   hipLaunchKernelGGL(k_cm_offsets, dim3(blocks(kNC + 1)), dim3(256), 0, stream_of(c), L->cube[w].as<int>(), (int)L->n[w],
                      L->off[w].as<int>());
-  MCHK(c, hipGetLastError());
+  LISLAM_HIPCHK(c, hipGetLastError());
   return LISLAM_OK;
 }
 
@@ -2229,21 +2187,21 @@ int cm_shift(lislam_lmap* L, int w, int si, int sj, int sk) {
   hipStream_t st = stream_of(c);
   const int n = (int)L->n[w];
   if (n == 0) return LISLAM_OK;
-  MCHK(c, L->keep.reserve((size_t)n * 4));
-  MCHK(c, L->tmp_cube.reserve((size_t)n * 4));
-  MCHK(c, L->tmp_pts.reserve((size_t)n * 16));
-  MCHK(c, L->counts.reserve(64));
+  LISLAM_HIPCHK(c, L->keep.reserve((size_t)n * 4));
+  LISLAM_HIPCHK(c, L->tmp_cube.reserve((size_t)n * 4));
+  LISLAM_HIPCHK(c, L->tmp_pts.reserve((size_t)n * 16));
+  LISLAM_HIPCHK(c, L->counts.reserve(64));
   hipLaunchKernelGGL(k_cm_shift, dim3(blocks(n)), dim3(256), 0, st, L->cube[w].as<int>(), n, si, sj, sk,
                      L->keep.as<int>(), L->tmp_cube.as<int>());
-  MCHK(c, L->sort_tmp.reserve(prims::select_temp_bytes(n)));
-  MCHK(c, prims::select_flagged(L->sort_tmp.p, L->pts[w].as<float4>(), L->keep.as<int>(), L->tmp_pts.as<float4>(),
-                                L->counts.as<int>(), n, st));
-  MCHK(c, prims::select_flagged(L->sort_tmp.p, L->tmp_cube.as<int>(), L->keep.as<int>(), L->cube[w].as<int>(),
-                                L->counts.as<int>() + 1, n, st));
+  LISLAM_HIPCHK(c, L->sort_tmp.reserve(prims::select_temp_bytes(n)));
+  LISLAM_HIPCHK(c, prims::select_flagged(L->sort_tmp.p, L->pts[w].as<float4>(), L->keep.as<int>(), L->tmp_pts.as<float4>(),
+                                         L->counts.as<int>(), n, st));
+  LISLAM_HIPCHK(c, prims::select_flagged(L->sort_tmp.p, L->tmp_cube.as<int>(), L->keep.as<int>(), L->cube[w].as<int>(),
+                                         L->counts.as<int>() + 1, n, st));
   int kept = 0;
-  MCHK(c, hipMemcpyAsync(&kept, L->counts.p, 4, hipMemcpyDeviceToHost, st));
-  MCHK(c, hipStreamSynchronize(st));
-  MCHK(c, hipMemcpyAsync(L->pts[w].p, L->tmp_pts.p, (size_t)kept * 16, hipMemcpyDeviceToDevice, st));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(&kept, L->counts.p, 4, hipMemcpyDeviceToHost, st));
+  LISLAM_HIPCHK(c, hipStreamSynchronize(st));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(L->pts[w].p, L->tmp_pts.p, (size_t)kept * 16, hipMemcpyDeviceToDevice, st));
   L->n[w] = kept;
   return cm_offsets(L, w);
 }
@@ -2255,44 +2213,44 @@ int cm_update(lislam_lmap* L, int w, const float4* stack, const int* n_stack, in
   hipStream_t st = stream_of(c);
   const int np = (int)L->n[w], nn = n_stack_host, m = np + nn;
   const float inv = 1.0f / L->res[w];
-  MCHK(c, L->newp.reserve((size_t)std::max(nn, 1) * 16));
-  MCHK(c, L->ncube.reserve((size_t)std::max(nn, 1) * 4));
+  LISLAM_HIPCHK(c, L->newp.reserve((size_t)std::max(nn, 1) * 16));
+  LISLAM_HIPCHK(c, L->ncube.reserve((size_t)std::max(nn, 1) * 4));
   if (nn > 0)
     hipLaunchKernelGGL(k_cm_newpts, dim3(blocks(nn)), dim3(256), 0, st, stack, n_stack, L->x.as<double>(), L->cen[0],
                        L->cen[1], L->cen[2], L->newp.as<float4>(), L->ncube.as<int>());
   if (m == 0) return LISLAM_OK;
-  MCHK(c, L->seg.reserve((size_t)std::max(nvalid, 1) * sizeof(CubeSeg)));
+  LISLAM_HIPCHK(c, L->seg.reserve((size_t)std::max(nvalid, 1) * sizeof(CubeSeg)));
   if (nvalid > 0)
     hipLaunchKernelGGL(k_cm_bounds, dim3(nvalid), dim3(256), 0, st, L->valid.as<int>(), L->off[w].as<int>(),
                        L->pts[w].as<float4>(), L->newp.as<float4>(), L->ncube.as<int>(), n_stack, inv, L->seg.as<CubeSeg>());
-  MCHK(c, L->keys.reserve((size_t)m * 8));
-  MCHK(c, L->keys2.reserve((size_t)m * 8));
-  MCHK(c, L->idx.reserve((size_t)m * 4));
-  MCHK(c, L->idx2.reserve((size_t)m * 4));
-  MCHK(c, L->flag.reserve((size_t)m * 4));
-  MCHK(c, L->pos.reserve((size_t)m * 4));
+  LISLAM_HIPCHK(c, L->keys.reserve((size_t)m * 8));
+  LISLAM_HIPCHK(c, L->keys2.reserve((size_t)m * 8));
+  LISLAM_HIPCHK(c, L->idx.reserve((size_t)m * 4));
+  LISLAM_HIPCHK(c, L->idx2.reserve((size_t)m * 4));
+  LISLAM_HIPCHK(c, L->flag.reserve((size_t)m * 4));
+  LISLAM_HIPCHK(c, L->pos.reserve((size_t)m * 4));
   hipLaunchKernelGGL(k_cm_keys, dim3(blocks(m)), dim3(256), 0, st, L->pts[w].as<float4>(), L->cube[w].as<int>(), np,
                      L->newp.as<float4>(), L->ncube.as<int>(), n_stack, L->vrank.as<int>(), L->seg.as<CubeSeg>(), inv,
                      L->keys.as<uint64_t>(), L->idx.as<int>());
-  MRC(sort_pairs_u64(c, L->sort_tmp, L->keys.as<uint64_t>(), L->keys2.as<uint64_t>(), L->idx.as<int>(),
-                     L->idx2.as<int>(), m));
+  LISLAM_RC(sort_pairs_u64(c, L->sort_tmp, L->keys.as<uint64_t>(), L->keys2.as<uint64_t>(), L->idx.as<int>(),
+                           L->idx2.as<int>(), m));
   hipLaunchKernelGGL(k_cm_runs, dim3(blocks(m)), dim3(256), 0, st, L->keys2.as<uint64_t>(), n_stack, np, L->flag.as<int>());
-  MCHK(c, L->sort_tmp.reserve(prims::exclusive_sum_temp_bytes(m)));
-  MCHK(c, prims::exclusive_sum(L->sort_tmp.p, L->flag.as<int>(), L->pos.as<int>(), m, st));
-  MCHK(c, L->tmp_pts.reserve((size_t)m * 16));
-  MCHK(c, L->tmp_cube.reserve((size_t)m * 4));
-  MCHK(c, L->counts.reserve(64));
+  LISLAM_HIPCHK(c, L->sort_tmp.reserve(prims::exclusive_sum_temp_bytes(m)));
+  LISLAM_HIPCHK(c, prims::exclusive_sum(L->sort_tmp.p, L->flag.as<int>(), L->pos.as<int>(), m, st));
+  LISLAM_HIPCHK(c, L->tmp_pts.reserve((size_t)m * 16));
+  LISLAM_HIPCHK(c, L->tmp_cube.reserve((size_t)m * 4));
+  LISLAM_HIPCHK(c, L->counts.reserve(64));
   hipLaunchKernelGGL(k_cm_centroids, dim3(blocks(m)), dim3(256), 0, st, L->pts[w].as<float4>(), np, L->newp.as<float4>(),
                      n_stack, L->keys2.as<uint64_t>(), L->idx2.as<int>(), L->pos.as<int>(), L->flag.as<int>(),
                      L->tmp_pts.as<float4>(), L->tmp_cube.as<int>(), L->counts.as<int>() + 2);
-  MCHK(c, hipGetLastError());
+  LISLAM_HIPCHK(c, hipGetLastError());
   int nout = 0;
-  MCHK(c, hipMemcpyAsync(&nout, L->counts.as<int>() + 2, 4, hipMemcpyDeviceToHost, st));
-  MCHK(c, hipStreamSynchronize(st));
-  MCHK(c, L->pts[w].reserve((size_t)std::max(nout, 1) * 16));
-  MCHK(c, L->cube[w].reserve((size_t)std::max(nout, 1) * 4));
-  MCHK(c, hipMemcpyAsync(L->pts[w].p, L->tmp_pts.p, (size_t)nout * 16, hipMemcpyDeviceToDevice, st));
-  MCHK(c, hipMemcpyAsync(L->cube[w].p, L->tmp_cube.p, (size_t)nout * 4, hipMemcpyDeviceToDevice, st));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(&nout, L->counts.as<int>() + 2, 4, hipMemcpyDeviceToHost, st));
+  LISLAM_HIPCHK(c, hipStreamSynchronize(st));
+  LISLAM_HIPCHK(c, L->pts[w].reserve((size_t)std::max(nout, 1) * 16));
+  LISLAM_HIPCHK(c, L->cube[w].reserve((size_t)std::max(nout, 1) * 4));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(L->pts[w].p, L->tmp_pts.p, (size_t)nout * 16, hipMemcpyDeviceToDevice, st));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(L->cube[w].p, L->tmp_cube.p, (size_t)nout * 4, hipMemcpyDeviceToDevice, st));
   L->n[w] = nout;
   return cm_offsets(L, w);
 }
@@ -2322,7 +2280,7 @@ int lislam_lmap_create(lislam_ctx* c, float line_res, float plane_res, lislam_lm
   if (rc) {
     for (auto* m : L->maps) lislam_map_destroy(m);
     delete L;
-    return mfail(c, LISLAM_ERR_DEVICE, "lislam_lmap_create failed");
+    return fail(c, LISLAM_ERR_DEVICE, "lislam_lmap_create failed");
   }
   *out = L;
   return LISLAM_OK;
@@ -2345,8 +2303,8 @@ int lislam_lmap_counts(lislam_lmap* L, int32_t* corner_counts, int32_t* surf_cou
   for (int w = 0; w < 2; w++) {
     if (!dst[w]) continue;
     std::vector<int> off(kNC + 1);
-    MCHK(c, hipMemcpyAsync(off.data(), L->off[w].p, off.size() * 4, hipMemcpyDeviceToHost, c->stream));
-    MCHK(c, hipStreamSynchronize(c->stream));
+    LISLAM_HIPCHK(c, hipMemcpyAsync(off.data(), L->off[w].p, off.size() * 4, hipMemcpyDeviceToHost, c->stream));
+    LISLAM_HIPCHK(c, hipStreamSynchronize(c->stream));
     for (int k = 0; k < kNC; k++) dst[w][k] = off[k + 1] - off[k];
   }
   return LISLAM_OK;
@@ -2358,10 +2316,10 @@ int lislam_lmap_points(lislam_lmap* L, int32_t which, float* out, int64_t cap, i
   hipSetDevice(c->device);
   *n = L->n[which];
   if (!out) return LISLAM_OK;
-  if (L->n[which] > cap) return mfail(c, LISLAM_ERR_CAPACITY, "lislam_lmap_points: %lld points, cap %lld",
-                                      (long long)L->n[which], (long long)cap);
-  if (L->n[which]) MCHK(c, hipMemcpyAsync(out, L->pts[which].p, (size_t)L->n[which] * 16, hipMemcpyDefault, c->stream));
-  MCHK(c, hipStreamSynchronize(c->stream));
+  if (L->n[which] > cap) return fail(c, LISLAM_ERR_CAPACITY, "lislam_lmap_points: %lld points, cap %lld",
+                                     (long long)L->n[which], (long long)cap);
+  if (L->n[which]) LISLAM_HIPCHK(c, hipMemcpyAsync(out, L->pts[which].p, (size_t)L->n[which] * 16, hipMemcpyDefault, c->stream));
+  LISLAM_HIPCHK(c, hipStreamSynchronize(c->stream));
   return LISLAM_OK;
 }
 
@@ -2392,7 +2350,7 @@ int lislam_lmap_step(lislam_lmap* L, const float* corner_last, int32_t nc, const
     while (cc[a] >= dims[a] - 3) { cc[a]--; L->cen[a]--; sh[a]--; }
   }
   if (sh[0] || sh[1] || sh[2])
-    for (int w = 0; w < 2; w++) MRC(cm_shift(L, w, sh[0], sh[1], sh[2]));
+    for (int w = 0; w < 2; w++) LISLAM_RC(cm_shift(L, w, sh[0], sh[1], sh[2]));
   // valid cubes in the reference's loop order (:566-588)
   std::vector<int> valid;
   for (int i = cc[0] - 2; i <= cc[0] + 2; i++)
@@ -2400,15 +2358,15 @@ int lislam_lmap_step(lislam_lmap* L, const float* corner_last, int32_t nc, const
       for (int k = cc[2] - 1; k <= cc[2] + 1; k++)
         if (i >= 0 && i < kW && j >= 0 && j < kH && k >= 0 && k < kD) valid.push_back(i + kW * j + kW * kH * k);
   const int nvalid = (int)valid.size();
-  MCHK(c, hipMemcpyAsync(L->valid.p, valid.data(), (size_t)nvalid * 4, hipMemcpyHostToDevice, st));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(L->valid.p, valid.data(), (size_t)nvalid * 4, hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(k_cm_vrank, dim3(blocks(kNC)), dim3(256), 0, st, L->vrank.as<int>());
   hipLaunchKernelGGL(k_cm_vrank_set, dim3(1), dim3(128), 0, st, L->valid.as<int>(), nvalid, L->vrank.as<int>());
   // local maps (:590-602)
-  MCHK(c, L->counts.reserve(64));
+  LISLAM_HIPCHK(c, L->counts.reserve(64));
   int* dcnt = L->counts.as<int>() + 8;  // [8, 10) local map sizes, [10, 12) stack sizes
-  MCHK(c, hipMemsetAsync(dcnt, 0, 16, st));
+  LISLAM_HIPCHK(c, hipMemsetAsync(dcnt, 0, 16, st));
   for (int w = 0; w < 2; w++) {
-    MCHK(c, L->local[w].reserve((size_t)std::max<int64_t>(L->n[w], 1) * 16));
+    LISLAM_HIPCHK(c, L->local[w].reserve((size_t)std::max<int64_t>(L->n[w], 1) * 16));
     if (nvalid > 0 && L->n[w] > 0)
       hipLaunchKernelGGL(k_cm_gather, dim3(nvalid), dim3(256), 0, st, L->valid.as<int>(), nvalid, L->off[w].as<int>(),
                          L->pts[w].as<float4>(), L->local[w].as<float4>(), dcnt + w);
@@ -2418,13 +2376,13 @@ int lislam_lmap_step(lislam_lmap* L, const float* corner_last, int32_t nc, const
   const int nlast[2] = {nc, ns};
   for (int w = 0; w < 2; w++) {
     DBuf& q = w == 0 ? L->sc.qc : L->sc.qs;
-    MRC(stage_points(c, L->sc, q, last[w], nlast[w], 4));
-    MCHK(c, L->stack[w].reserve((size_t)std::max(nlast[w], 1) * 16));
-    MRC(voxel_grid_device(c, L->sc, q.as<float4>(), nlast[w], L->res[w], L->stack[w].as<float4>(), dcnt + 2 + w));
+    LISLAM_RC(stage_points(c, L->sc, q, last[w], nlast[w], 4));
+    LISLAM_HIPCHK(c, L->stack[w].reserve((size_t)std::max(nlast[w], 1) * 16));
+    LISLAM_RC(voxel_grid_device(c, L->sc, q.as<float4>(), nlast[w], L->res[w], L->stack[w].as<float4>(), dcnt + 2 + w));
   }
   int h4[4] = {0, 0, 0, 0};
-  MCHK(c, hipMemcpyAsync(h4, dcnt, 16, hipMemcpyDeviceToHost, st));
-  MCHK(c, hipStreamSynchronize(st));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(h4, dcnt, 16, hipMemcpyDeviceToHost, st));
+  LISLAM_HIPCHK(c, hipStreamSynchronize(st));
   const int ncm = h4[0], nsm = h4[1], ncs = h4[2], nss = h4[3];
   if (stats) {
     stats[0] = ncm; stats[1] = nsm; stats[2] = ncs; stats[3] = nss;
@@ -2432,10 +2390,10 @@ int lislam_lmap_step(lislam_lmap* L, const float* corner_last, int32_t nc, const
   }
   // the optimization (:620-857) when the map is large enough
   if (ncm > 10 && nsm > 50) {
-    MRC(lislam_map_build(L->maps[0], L->local[0].as<float>(), ncm, 4));
-    MRC(lislam_map_build(L->maps[1], L->local[1].as<float>(), nsm, 4));
+    LISLAM_RC(lislam_map_build(L->maps[0], L->local[0].as<float>(), ncm, 4));
+    LISLAM_RC(lislam_map_build(L->maps[1], L->local[1].as<float>(), nsm, 4));
     int s4[4];
-    MRC(lislam_laser_mapping(L->maps[0], L->maps[1], L->stack[0].as<float>(), ncs, L->stack[1].as<float>(), nss, x, s4));
+    LISLAM_RC(lislam_laser_mapping(L->maps[0], L->maps[1], L->stack[0].as<float>(), ncs, L->stack[1].as<float>(), nss, x, s4));
     if (stats) for (int k = 0; k < 4; k++) stats[4 + k] = s4[k];
   }
   // transformUpdate (:145-149) with Eigen's Quaternion::inverse (conjugate / squaredNorm)
@@ -2450,9 +2408,9 @@ int lislam_lmap_step(lislam_lmap* L, const float* corner_last, int32_t nc, const
     for (int k = 0; k < 3; k++) tm[k] = x[4 + k] - r[k];
   }
   // insertion at the optimized pose and the VoxelGrid of the valid cubes (:880-1002)
-  MCHK(c, hipMemcpyAsync(L->x.p, x, 56, hipMemcpyHostToDevice, st));
-  MRC(cm_update(L, 0, L->stack[0].as<float4>(), dcnt + 2, ncs, nvalid));
-  MRC(cm_update(L, 1, L->stack[1].as<float4>(), dcnt + 3, nss, nvalid));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(L->x.p, x, 56, hipMemcpyHostToDevice, st));
+  LISLAM_RC(cm_update(L, 0, L->stack[0].as<float4>(), dcnt + 2, ncs, nvalid));
+  LISLAM_RC(cm_update(L, 1, L->stack[1].as<float4>(), dcnt + 3, nss, nvalid));
   if (out_pose) for (int e = 0; e < 7; e++) out_pose[e] = x[e];
   return LISLAM_OK;
 }
@@ -2770,27 +2728,27 @@ int lc_prepare(lislam_ctx* c, LoopState& ls, int n, const lislam_icp_config* cfg
   hipStream_t st = stream_of(c);
   MapScratch& sc = ctx_scratch(c);
   *n_out = 0;
-  MCHK(c, dst.reserve((size_t)std::max(n, 1) * sizeof(float4)));
+  LISLAM_HIPCHK(c, dst.reserve((size_t)std::max(n, 1) * sizeof(float4)));
   if (n == 0) return LISLAM_OK;
-  MCHK(c, ls.flag.reserve((size_t)n));
-  MCHK(c, ls.sel.reserve((size_t)n * sizeof(float4)));
-  MCHK(c, ls.cnt.reserve(16));
+  LISLAM_HIPCHK(c, ls.flag.reserve((size_t)n));
+  LISLAM_HIPCHK(c, ls.sel.reserve((size_t)n * sizeof(float4)));
+  LISLAM_HIPCHK(c, ls.cnt.reserve(16));
   hipLaunchKernelGGL(k_lc_flags, dim3(blocks(n)), dim3(256), 0, st, ls.tf.as<float4>(), n, cfg->use_crop ? 1 : 0,
                      -cfg->crop_size, cfg->crop_size, ls.flag.as<uint8_t>());
-  MCHK(c, ls.tmp.reserve(prims::select_temp_bytes(n)));
-  MCHK(c, prims::select_flagged(ls.tmp.p, ls.tf.as<float4>(), ls.flag.as<uint8_t>(), ls.sel.as<float4>(), ls.cnt.as<int>(), n,
-                                st));
+  LISLAM_HIPCHK(c, ls.tmp.reserve(prims::select_temp_bytes(n)));
+  LISLAM_HIPCHK(c, prims::select_flagged(ls.tmp.p, ls.tf.as<float4>(), ls.flag.as<uint8_t>(), ls.sel.as<float4>(), ls.cnt.as<int>(), n,
+                                         st));
   int m = 0;
-  MCHK(c, hipMemcpyAsync(&m, ls.cnt.p, sizeof(int), hipMemcpyDeviceToHost, st));
-  MCHK(c, hipStreamSynchronize(st));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(&m, ls.cnt.p, sizeof(int), hipMemcpyDeviceToHost, st));
+  LISLAM_HIPCHK(c, hipStreamSynchronize(st));
   if (!cfg->use_downsample || m == 0) {
-    if (m) MCHK(c, hipMemcpyAsync(dst.p, ls.sel.p, (size_t)m * sizeof(float4), hipMemcpyDeviceToDevice, st));
+    if (m) LISLAM_HIPCHK(c, hipMemcpyAsync(dst.p, ls.sel.p, (size_t)m * sizeof(float4), hipMemcpyDeviceToDevice, st));
     *n_out = m;
     return LISLAM_OK;
   }
-  MRC(voxel_grid_device(c, sc, ls.sel.as<float4>(), m, cfg->voxel_size, dst.as<float4>(), ls.cnt.as<int>() + 1));
-  MCHK(c, hipMemcpyAsync(n_out, ls.cnt.as<int>() + 1, sizeof(int), hipMemcpyDeviceToHost, st));
-  MCHK(c, hipStreamSynchronize(st));
+  LISLAM_RC(voxel_grid_device(c, sc, ls.sel.as<float4>(), m, cfg->voxel_size, dst.as<float4>(), ls.cnt.as<int>() + 1));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(n_out, ls.cnt.as<int>() + 1, sizeof(int), hipMemcpyDeviceToHost, st));
+  LISLAM_HIPCHK(c, hipStreamSynchronize(st));
   return LISLAM_OK;
 }
 
@@ -2803,14 +2761,14 @@ int lislam_loop_icp(lislam_ctx* c, const lislam_icp_config* cfg, const float* cu
                     double* T_cur2map, double* fitness, int32_t* info) {
   if (!c || !cfg || n_cur < 0 || (n_cur > 0 && !cur) || !T_cur || n_hist < 0 || (n_hist > 0 && (!hist_counts || !T_hist)))
     return LISLAM_ERR_ARG;
-  if (cfg->use_downsample && !(cfg->voxel_size > 0)) return mfail(c, LISLAM_ERR_ARG, "lislam_loop_icp: voxel_size <= 0");
+  if (cfg->use_downsample && !(cfg->voxel_size > 0)) return fail(c, LISLAM_ERR_ARG, "lislam_loop_icp: voxel_size <= 0");
   int64_t n_h = 0;
   for (int h = 0; h < n_hist; h++) {
     if (hist_counts[h] < 0) return LISLAM_ERR_ARG;
     n_h += hist_counts[h];
   }
   if (n_h > 0 && !hist) return LISLAM_ERR_ARG;
-  if (n_h > 0x3fffffff || n_cur > 0x3fffffff) return mfail(c, LISLAM_ERR_CAPACITY, "lislam_loop_icp: clouds too large");
+  if (n_h > 0x3fffffff || n_cur > 0x3fffffff) return fail(c, LISLAM_ERR_CAPACITY, "lislam_loop_icp: clouds too large");
   hipSetDevice(c->device);
   hipStream_t st = stream_of(c);
   MapScratch& sc = ctx_scratch(c);
@@ -2819,7 +2777,7 @@ int lislam_loop_icp(lislam_ctx* c, const lislam_icp_config* cfg, const float* cu
     sc.loop->map.ctx = c;
   }
   LoopState& ls = *sc.loop;
-  if (!ls.host) return mfail(c, LISLAM_ERR_DEVICE, "lislam_loop_icp: pinned allocation failed");
+  if (!ls.host) return fail(c, LISLAM_ERR_DEVICE, "lislam_loop_icp: pinned allocation failed");
   int32_t inf[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   double Ti[16], Tc[16], fit = DBL_MAX;
   for (int k = 0; k < 16; k++) { Ti[k] = (k % 5 == 0) ? 1.0 : 0.0; Tc[k] = T_cur[k]; }
@@ -2832,20 +2790,20 @@ int lislam_loop_icp(lislam_ctx* c, const lislam_icp_config* cfg, const float* cu
   };
   // stage + transform: the current keyframe, then the history keyframes in order
   const int64_t ntot = std::max<int64_t>(n_cur, n_h);
-  MCHK(c, ls.raw.reserve((size_t)std::max<int64_t>(ntot, 1) * sizeof(float4)));
-  MCHK(c, ls.tf.reserve((size_t)std::max<int64_t>(ntot, 1) * sizeof(float4)));
+  LISLAM_HIPCHK(c, ls.raw.reserve((size_t)std::max<int64_t>(ntot, 1) * sizeof(float4)));
+  LISLAM_HIPCHK(c, ls.tf.reserve((size_t)std::max<int64_t>(ntot, 1) * sizeof(float4)));
   if (n_h == 0) {
     inf[0] = -1;
     return finish();
   }
   int ns = 0, nt = 0;
-  if (n_cur) MCHK(c, hipMemcpyAsync(ls.raw.p, cur, (size_t)n_cur * 16, hipMemcpyDefault, st));
+  if (n_cur) LISLAM_HIPCHK(c, hipMemcpyAsync(ls.raw.p, cur, (size_t)n_cur * 16, hipMemcpyDefault, st));
   lc_transform(c, ls.raw.as<float4>(), n_cur, T_cur, ls.tf.as<float4>());
-  MRC(lc_prepare(c, ls, n_cur, cfg, ls.src0, &ns));
-  MCHK(c, hipMemcpyAsync(ls.raw.p, hist, (size_t)n_h * 16, hipMemcpyDefault, st));
+  LISLAM_RC(lc_prepare(c, ls, n_cur, cfg, ls.src0, &ns));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(ls.raw.p, hist, (size_t)n_h * 16, hipMemcpyDefault, st));
   for (int h = 0, off = 0; h < n_hist; off += hist_counts[h], h++)
     lc_transform(c, ls.raw.as<float4>() + off, hist_counts[h], T_hist + 16 * h, ls.tf.as<float4>() + off);
-  MRC(lc_prepare(c, ls, (int)n_h, cfg, ls.tgt, &nt));
+  LISLAM_RC(lc_prepare(c, ls, (int)n_h, cfg, ls.tgt, &nt));
   inf[4] = ns;
   inf[5] = nt;
   if (ns <= 10 || nt <= 10) {
@@ -2856,24 +2814,24 @@ int lislam_loop_icp(lislam_ctx* c, const lislam_icp_config* cfg, const float* cu
   lislam_map& m = ls.map;
   m.cell = std::max(1.0f, cfg->use_downsample ? 2.0f * cfg->voxel_size : 1.0f);
   m.ds = m.cell;
-  MCHK(c, m.tmp.reserve((size_t)nt * sizeof(float4)));
+  LISLAM_HIPCHK(c, m.tmp.reserve((size_t)nt * sizeof(float4)));
   hipLaunchKernelGGL(k_lc_ids, dim3(blocks(nt)), dim3(256), 0, st, ls.tgt.as<float4>(), nt, m.tmp.as<float4>());
-  MRC(rebuild(&m, nt));
+  LISLAM_RC(rebuild(&m, nt));
   // ICP state
-  MCHK(c, ls.src.reserve((size_t)ns * sizeof(float4)));
-  MCHK(c, ls.ftf.reserve((size_t)ns * sizeof(float4)));
-  MCHK(c, ls.nb.reserve((size_t)ns * sizeof(float4)));
-  MCHK(c, ls.d2.reserve((size_t)ns * 4));
-  MCHK(c, ls.found.reserve((size_t)ns * 4));
-  MCHK(c, ls.st.reserve(sizeof(IcpDev)));
-  MCHK(c, hipMemcpyAsync(ls.src.p, ls.src0.p, (size_t)ns * sizeof(float4), hipMemcpyDeviceToDevice, st));
+  LISLAM_HIPCHK(c, ls.src.reserve((size_t)ns * sizeof(float4)));
+  LISLAM_HIPCHK(c, ls.ftf.reserve((size_t)ns * sizeof(float4)));
+  LISLAM_HIPCHK(c, ls.nb.reserve((size_t)ns * sizeof(float4)));
+  LISLAM_HIPCHK(c, ls.d2.reserve((size_t)ns * 4));
+  LISLAM_HIPCHK(c, ls.found.reserve((size_t)ns * 4));
+  LISLAM_HIPCHK(c, ls.st.reserve(sizeof(IcpDev)));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(ls.src.p, ls.src0.p, (size_t)ns * sizeof(float4), hipMemcpyDeviceToDevice, st));
   IcpDev* h = ls.host;
   std::memset(h, 0, sizeof(IcpDev));
   for (int k = 0; k < 16; k++) h->T[k] = h->F[k] = (k % 5 == 0) ? 1.f : 0.f;
   h->prev_mse = DBL_MAX;
   h->nq = ns;
   IcpDev* d = ls.st.as<IcpDev>();
-  MCHK(c, hipMemcpyAsync(d, h, sizeof(IcpDev), hipMemcpyHostToDevice, st));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(d, h, sizeof(IcpDev), hipMemcpyHostToDevice, st));
   IcpParams P;
   P.max_iter = cfg->max_iterations;
   P.rot_thr = 1.0 - cfg->transformation_epsilon;
@@ -2885,8 +2843,8 @@ int lislam_loop_icp(lislam_ctx* c, const lislam_icp_config* cfg, const float* cu
   constexpr int kChunk = 6;
   for (int it0 = 0; it0 < cap; it0 += kChunk) {
     for (int j = 0; j < kChunk && it0 + j < cap; j++) {
-      MRC(knn_device(&m, ls.src.as<float>(), 4, &d->nq, ns, nullptr, 1, md2, ls.nb.as<float4>(), ls.d2.as<float>(),
-                     ls.found.as<int>()));
+      LISLAM_RC(knn_device(&m, ls.src.as<float>(), 4, &d->nq, ns, nullptr, 1, md2, ls.nb.as<float4>(), ls.d2.as<float>(),
+                           ls.found.as<int>()));
       {
         TimedScope ts(c, kT_icp_step);
         hipLaunchKernelGGL(k_lc_step, dim3(1), dim3(kRed), 0, st, d, ls.src.as<float4>(), ls.nb.as<float4>(),
@@ -2895,19 +2853,19 @@ int lislam_loop_icp(lislam_ctx* c, const lislam_icp_config* cfg, const float* cu
       TimedScope ts(c, kT_icp_apply);
       hipLaunchKernelGGL(k_lc_apply, dim3(blocks(ns)), dim3(256), 0, st, d, ls.src.as<float4>(), ns);
     }
-    MCHK(c, hipMemcpyAsync(h, d, sizeof(IcpDev), hipMemcpyDeviceToHost, st));
-    MCHK(c, hipStreamSynchronize(st));
+    LISLAM_HIPCHK(c, hipMemcpyAsync(h, d, sizeof(IcpDev), hipMemcpyDeviceToHost, st));
+    LISLAM_HIPCHK(c, hipStreamSynchronize(st));
     if (h->done) break;
   }
-  if (!h->done) return mfail(c, LISLAM_ERR_STATE, "lislam_loop_icp: iteration loop did not terminate");
+  if (!h->done) return fail(c, LISLAM_ERR_STATE, "lislam_loop_icp: iteration loop did not terminate");
   // fitness
   hipLaunchKernelGGL(k_lc_final_tf, dim3(blocks(ns)), dim3(256), 0, st, d, ls.src0.as<float4>(), ns, ls.ftf.as<float4>());
-  MRC(knn_device(&m, ls.ftf.as<float>(), 4, nullptr, ns, nullptr, 1, mapk::kInf, ls.nb.as<float4>(), ls.d2.as<float>(),
-                 ls.found.as<int>()));
+  LISLAM_RC(knn_device(&m, ls.ftf.as<float>(), 4, nullptr, ns, nullptr, 1, mapk::kInf, ls.nb.as<float4>(), ls.d2.as<float>(),
+                       ls.found.as<int>()));
   hipLaunchKernelGGL(k_lc_fitness, dim3(1), dim3(kRed), 0, st, d, ls.d2.as<float>(), ls.found.as<int>(), ns);
-  MCHK(c, hipGetLastError());
-  MCHK(c, hipMemcpyAsync(h, d, sizeof(IcpDev), hipMemcpyDeviceToHost, st));
-  MCHK(c, hipStreamSynchronize(st));
+  LISLAM_HIPCHK(c, hipGetLastError());
+  LISLAM_HIPCHK(c, hipMemcpyAsync(h, d, sizeof(IcpDev), hipMemcpyDeviceToHost, st));
+  LISLAM_HIPCHK(c, hipStreamSynchronize(st));
   fit = h->fitness;
   inf[1] = (h->state >= 1 && h->state <= 4) ? 1 : 0;
   inf[2] = h->state;
@@ -3261,9 +3219,9 @@ namespace {
 
 template <typename T>
 int lv_upload(lislam_ctx* c, DBuf& d, const std::vector<T>& v) {
-  MCHK(c, d.reserve(std::max<size_t>(v.size() * sizeof(T), 16)));
+  LISLAM_HIPCHK(c, d.reserve(std::max<size_t>(v.size() * sizeof(T), 16)));
   // pageable source: the copy has read it when it returns
-  if (!v.empty()) MCHK(c, hipMemcpyAsync(d.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, stream_of(c)));
+  if (!v.empty()) LISLAM_HIPCHK(c, hipMemcpyAsync(d.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, stream_of(c)));
   return LISLAM_OK;
 }
 
@@ -3280,7 +3238,7 @@ extern "C" {
 int lislam_keyframes_create(lislam_ctx* c, int32_t capacity, int64_t point_capacity, lislam_keyframes** out) {
   if (!c || !out) return LISLAM_ERR_ARG;
   *out = nullptr;
-  if (capacity < 1 || point_capacity < 0) return mfail(c, LISLAM_ERR_ARG, "lislam_keyframes_create: invalid capacity");
+  if (capacity < 1 || point_capacity < 0) return fail(c, LISLAM_ERR_ARG, "lislam_keyframes_create: invalid capacity");
   hipSetDevice(c->device);
   lislam_keyframes* kf = new lislam_keyframes();
   kf->ctx = c;
@@ -3289,7 +3247,7 @@ int lislam_keyframes_create(lislam_ctx* c, int32_t capacity, int64_t point_capac
   if (hipMalloc((void**)&kf->pts, (size_t)std::max<int64_t>(point_capacity, 1) * sizeof(float4)) != hipSuccess) {
     (void)hipGetLastError();
     delete kf;
-    return mfail(c, LISLAM_ERR_DEVICE, "lislam_keyframes_create: allocating %lld points failed", (long long)point_capacity);
+    return fail(c, LISLAM_ERR_DEVICE, "lislam_keyframes_create: allocating %lld points failed", (long long)point_capacity);
   }
   kf->off.reserve((size_t)capacity + 1);
   *out = kf;
@@ -3317,21 +3275,21 @@ int lislam_keyframes_add_clouds(lislam_keyframes* kf, const void* points, const 
   lislam_ctx* c = kf->ctx;
   int64_t total = 0;
   for (int k = 0; k < n_clouds; k++) {
-    if (counts[k] < 0) return mfail(c, LISLAM_ERR_ARG, "lislam_keyframes_add_clouds: counts[%d] = %d", k, counts[k]);
+    if (counts[k] < 0) return fail(c, LISLAM_ERR_ARG, "lislam_keyframes_add_clouds: counts[%d] = %d", k, counts[k]);
     total += counts[k];
   }
-  if (total > 0 && !points) return mfail(c, LISLAM_ERR_ARG, "lislam_keyframes_add_clouds: null points");
+  if (total > 0 && !points) return fail(c, LISLAM_ERR_ARG, "lislam_keyframes_add_clouds: null points");
   if ((int64_t)kf->size() + n_clouds > kf->capacity)
-    return mfail(c, LISLAM_ERR_CAPACITY, "lislam_keyframes_add_clouds: %d + %d keyframes exceed the capacity %d", kf->size(),
-                 n_clouds, kf->capacity);
+    return fail(c, LISLAM_ERR_CAPACITY, "lislam_keyframes_add_clouds: %d + %d keyframes exceed the capacity %d", kf->size(),
+                n_clouds, kf->capacity);
   if (kf->off.back() + total > kf->point_capacity)
-    return mfail(c, LISLAM_ERR_CAPACITY, "lislam_keyframes_add_clouds: %lld + %lld points exceed the capacity %lld",
-                 (long long)kf->off.back(), (long long)total, (long long)kf->point_capacity);
+    return fail(c, LISLAM_ERR_CAPACITY, "lislam_keyframes_add_clouds: %lld + %lld points exceed the capacity %lld",
+                (long long)kf->off.back(), (long long)total, (long long)kf->point_capacity);
   if (n_clouds == 0) return LISLAM_OK;
   hipSetDevice(c->device);
   if (total > 0) {
-    MCHK(c, hipMemcpyAsync(kf->pts + kf->off.back(), points, (size_t)total * sizeof(float4), hipMemcpyDefault, stream_of(c)));
-    MCHK(c, hipStreamSynchronize(stream_of(c)));  // the caller's array is free on return
+    LISLAM_HIPCHK(c, hipMemcpyAsync(kf->pts + kf->off.back(), points, (size_t)total * sizeof(float4), hipMemcpyDefault, stream_of(c)));
+    LISLAM_HIPCHK(c, hipStreamSynchronize(stream_of(c)));  // the caller's array is free on return
   }
   for (int k = 0; k < n_clouds; k++) kf->off.push_back(kf->off.back() + counts[k]);
   return LISLAM_OK;
@@ -3340,25 +3298,20 @@ int lislam_keyframes_add_clouds(lislam_keyframes* kf, const void* points, const 
 int lislam_keyframes_add_batch(lislam_keyframes* kf, lislam_batch* b, int32_t first_scan, int32_t n_scans) {
   if (!kf || !b) return LISLAM_ERR_ARG;
   lislam_ctx* c = kf->ctx;
-  if (b->ctx != c) return mfail(c, LISLAM_ERR_ARG, "lislam_keyframes_add_batch: the batch belongs to another context");
-  if (first_scan < 0 || n_scans < 0 || (int64_t)first_scan + n_scans > b->max_scans)
-    return mfail(c, LISLAM_ERR_ARG, "lislam_keyframes_add_batch: scans [%d, %d + %d) out of range", first_scan, first_scan,
-                 n_scans);
-  if (!b->fa.track)
-    return mfail(c, LISLAM_ERR_STATE, "lislam_keyframes_add_batch: cloud_track not materialized (want_images=0)");
-  if (first_scan + n_scans > b->extracted)
-    return mfail(c, LISLAM_ERR_STATE, "lislam_keyframes_add_batch: extract %d scans first", first_scan + n_scans);
-  if ((int64_t)kf->size() + n_scans > kf->capacity)
-    return mfail(c, LISLAM_ERR_CAPACITY, "lislam_keyframes_add_batch: %d + %d keyframes exceed the capacity %d", kf->size(),
-                 n_scans, kf->capacity);
+  const char* who = "lislam_keyframes_add_batch";
+  LISLAM_RC(check_same_context(c, who, b));
+  LISLAM_RC(check_scan_range(c, who, b, first_scan, n_scans));
+  LISLAM_RC(check_cloud_track(c, who, b));
+  LISLAM_RC(check_extracted(c, who, b, first_scan, n_scans));
+  LISLAM_RC(check_capacity(c, who, kf->size(), n_scans, "keyframes", kf->capacity));
   const int64_t total = (int64_t)n_scans * b->N;
   if (kf->off.back() + total > kf->point_capacity)
-    return mfail(c, LISLAM_ERR_CAPACITY, "lislam_keyframes_add_batch: %lld + %lld points exceed the capacity %lld",
-                 (long long)kf->off.back(), (long long)total, (long long)kf->point_capacity);
+    return fail(c, LISLAM_ERR_CAPACITY, "lislam_keyframes_add_batch: %lld + %lld points exceed the capacity %lld",
+                (long long)kf->off.back(), (long long)total, (long long)kf->point_capacity);
   if (n_scans == 0) return LISLAM_OK;
   hipSetDevice(c->device);
-  MCHK(c, hipMemcpyAsync(kf->pts + kf->off.back(), reinterpret_cast<const float4*>(b->fa.track) + (size_t)first_scan * b->N,
-                         (size_t)total * sizeof(float4), hipMemcpyDeviceToDevice, stream_of(c)));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(kf->pts + kf->off.back(), reinterpret_cast<const float4*>(b->fa.track) + (size_t)first_scan * b->N,
+                                  (size_t)total * sizeof(float4), hipMemcpyDeviceToDevice, stream_of(c)));
   for (int k = 0; k < n_scans; k++) kf->off.push_back(kf->off.back() + b->N);
   return LISLAM_OK;
 }
@@ -3366,31 +3319,26 @@ int lislam_keyframes_add_batch(lislam_keyframes* kf, lislam_batch* b, int32_t fi
 int lislam_keyframes_add_batch_scans(lislam_keyframes* kf, lislam_batch* b, const int32_t* scans, int32_t n) {
   if (!kf || !b || n < 0 || (n > 0 && !scans)) return LISLAM_ERR_ARG;
   lislam_ctx* c = kf->ctx;
-  if (b->ctx != c) return mfail(c, LISLAM_ERR_ARG, "lislam_keyframes_add_batch_scans: the batch belongs to another context");
-  if (!b->fa.track)
-    return mfail(c, LISLAM_ERR_STATE, "lislam_keyframes_add_batch_scans: cloud_track not materialized (want_images=0)");
-  if (n > 0 && b->extracted < 1) return mfail(c, LISLAM_ERR_STATE, "lislam_keyframes_add_batch_scans: extract the batch first");
-  for (int k = 0; k < n; k++)
-    if (scans[k] < 0 || scans[k] >= b->extracted)
-      return mfail(c, LISLAM_ERR_ARG, "lislam_keyframes_add_batch_scans: scans[%d] = %d outside [0, %d)", k, scans[k],
-                   b->extracted);
-  if ((int64_t)kf->size() + n > kf->capacity)
-    return mfail(c, LISLAM_ERR_CAPACITY, "lislam_keyframes_add_batch_scans: %d + %d keyframes exceed the capacity %d", kf->size(),
-                 n, kf->capacity);
+  const char* who = "lislam_keyframes_add_batch_scans";
+  LISLAM_RC(check_same_context(c, who, b));
+  LISLAM_RC(check_cloud_track(c, who, b));
+  LISLAM_RC(check_extracted_any(c, who, b, n));
+  LISLAM_RC(check_index(c, who, "scans", scans, n, b->extracted, false));
+  LISLAM_RC(check_capacity(c, who, kf->size(), n, "keyframes", kf->capacity));
   const int64_t total = (int64_t)n * b->N;
   if (kf->off.back() + total > kf->point_capacity)
-    return mfail(c, LISLAM_ERR_CAPACITY, "lislam_keyframes_add_batch_scans: %lld + %lld points exceed the capacity %lld",
-                 (long long)kf->off.back(), (long long)total, (long long)kf->point_capacity);
+    return fail(c, LISLAM_ERR_CAPACITY, "lislam_keyframes_add_batch_scans: %lld + %lld points exceed the capacity %lld",
+                (long long)kf->off.back(), (long long)total, (long long)kf->point_capacity);
   if (n == 0) return LISLAM_OK;
   hipSetDevice(c->device);
-  MCHK(c, kf->list.reserve((size_t)n * sizeof(int)));
+  LISLAM_HIPCHK(c, kf->list.reserve((size_t)n * sizeof(int)));
   // pageable source: the copy has read it when it returns
-  MCHK(c, hipMemcpyAsync(kf->list.p, scans, (size_t)n * sizeof(int), hipMemcpyHostToDevice, stream_of(c)));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(kf->list.p, scans, (size_t)n * sizeof(int), hipMemcpyHostToDevice, stream_of(c)));
   const int parts = std::max(1, std::min(64, (b->N + 4 * loopk::kGather - 1) / (4 * loopk::kGather)));
   hipLaunchKernelGGL(loopk::k_kf_gather, dim3(parts, n), dim3(loopk::kGather), 0, stream_of(c),
                      reinterpret_cast<const float4*>(b->fa.track), static_cast<const int*>(kf->list.p), b->N,
                      kf->pts + kf->off.back());
-  MCHK(c, hipGetLastError());
+  LISLAM_HIPCHK(c, hipGetLastError());
   for (int k = 0; k < n; k++) kf->off.push_back(kf->off.back() + b->N);
   return LISLAM_OK;
 }
@@ -3399,15 +3347,15 @@ int lislam_keyframes_download(lislam_keyframes* kf, int32_t index, float* dst, i
   if (!kf || cap_points < 0 || (cap_points > 0 && !dst)) return LISLAM_ERR_ARG;
   lislam_ctx* c = kf->ctx;
   if (index < 0 || index >= kf->size())
-    return mfail(c, LISLAM_ERR_ARG, "lislam_keyframes_download: index %d out of range (size %d)", index, kf->size());
+    return fail(c, LISLAM_ERR_ARG, "lislam_keyframes_download: index %d out of range (size %d)", index, kf->size());
   const int64_t cnt = kf->off[index + 1] - kf->off[index];
   if (n) *n = (int32_t)cnt;
   if (cap_points < cnt)
-    return mfail(c, LISLAM_ERR_CAPACITY, "lislam_keyframes_download: %lld points, capacity %d", (long long)cnt, cap_points);
+    return fail(c, LISLAM_ERR_CAPACITY, "lislam_keyframes_download: %lld points, capacity %d", (long long)cnt, cap_points);
   if (cnt == 0) return LISLAM_OK;
   hipSetDevice(c->device);
-  MCHK(c, hipMemcpyAsync(dst, kf->pts + kf->off[index], (size_t)cnt * sizeof(float4), hipMemcpyDeviceToHost, stream_of(c)));
-  MCHK(c, hipStreamSynchronize(stream_of(c)));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(dst, kf->pts + kf->off[index], (size_t)cnt * sizeof(float4), hipMemcpyDeviceToHost, stream_of(c)));
+  LISLAM_HIPCHK(c, hipStreamSynchronize(stream_of(c)));
   return LISLAM_OK;
 }
 
@@ -3417,17 +3365,17 @@ int lislam_loop_verify(lislam_keyframes* kf, const lislam_icp_config* cfg, int32
   if (!kf || !cfg || n_loops < 0 || (n_loops > 0 && (!cur_id || !loop_id || !T_kf))) return LISLAM_ERR_ARG;
   lislam_ctx* c = kf->ctx;
   const int nk = kf->size(), w = submap_window, L = n_loops;
-  if (w < 0 || w > 4) return mfail(c, LISLAM_ERR_ARG, "lislam_loop_verify: submap_window %d not in 0..4", w);
-  if (cfg->use_downsample && !(cfg->voxel_size > 0)) return mfail(c, LISLAM_ERR_ARG, "lislam_loop_verify: voxel_size <= 0");
+  if (w < 0 || w > 4) return fail(c, LISLAM_ERR_ARG, "lislam_loop_verify: submap_window %d not in 0..4", w);
+  if (cfg->use_downsample && !(cfg->voxel_size > 0)) return fail(c, LISLAM_ERR_ARG, "lislam_loop_verify: voxel_size <= 0");
   for (int k = 0; k < L; k++) {
     if (cur_id[k] < 0 || cur_id[k] >= nk)
-      return mfail(c, LISLAM_ERR_ARG, "lislam_loop_verify: cur_id[%d] = %d out of range (size %d)", k, cur_id[k], nk);
+      return fail(c, LISLAM_ERR_ARG, "lislam_loop_verify: cur_id[%d] = %d out of range (size %d)", k, cur_id[k], nk);
     if (loop_id[k] >= nk || loop_id[k] > cur_id[k])
-      return mfail(c, LISLAM_ERR_ARG, "lislam_loop_verify: loop_id[%d] = %d with cur_id %d (size %d)", k, loop_id[k],
-                   cur_id[k], nk);
+      return fail(c, LISLAM_ERR_ARG, "lislam_loop_verify: loop_id[%d] = %d with cur_id %d (size %d)", k, loop_id[k],
+                  cur_id[k], nk);
   }
   if (L == 0) return LISLAM_OK;
-  if (L > 0x1fffffff) return mfail(c, LISLAM_ERR_CAPACITY, "lislam_loop_verify: too many candidates");
+  if (L > 0x1fffffff) return fail(c, LISLAM_ERR_CAPACITY, "lislam_loop_verify: too many candidates");
   // pieces and segments: 2k = the source of candidate k, 2k + 1 its target
   const int nseg = 2 * L;
   std::vector<LvPiece> pc;
@@ -3457,7 +3405,7 @@ int lislam_loop_verify(lislam_keyframes* kf, const lislam_icp_config* cfg, int32
     piece(cur, 2 * k);
     rawoff[2 * k + 1] = (int)std::min<int64_t>(tot, 0x3fffffff);
     for (int i = lo; i <= hi; i++) piece(i, 2 * k + 1);
-    if (tot > 0x3fffffff) return mfail(c, LISLAM_ERR_CAPACITY, "lislam_loop_verify: the candidates' clouds are too large");
+    if (tot > 0x3fffffff) return fail(c, LISLAM_ERR_CAPACITY, "lislam_loop_verify: the candidates' clouds are too large");
   }
   rawoff[nseg] = (int)tot;
   const int ntot = (int)tot;
@@ -3468,64 +3416,64 @@ int lislam_loop_verify(lislam_keyframes* kf, const lislam_icp_config* cfg, int32
   if (!sc.verify) sc.verify = new VerifyState();
   VerifyState& V = *sc.verify;
   V.hT.resize((size_t)nk * 16);
-  MCHK(c, hipMemcpy(V.hT.data(), T_kf, (size_t)nk * 16 * sizeof(double), hipMemcpyDefault));
+  LISLAM_HIPCHK(c, hipMemcpy(V.hT.data(), T_kf, (size_t)nk * 16 * sizeof(double), hipMemcpyDefault));
   const double* hT = V.hT.data();
 
   std::vector<int> ns(L, 0), nt(L, 0), act;  // prepared sizes; the candidates that iterate
   std::vector<LvCand> cd;
   IcpDev* hst = nullptr;
   if (ntot > 0) {
-    MRC(lv_upload(c, V.T, V.hT));
-    MRC(lv_upload(c, V.pieces, pc));
-    MRC(lv_upload(c, V.pdst, pdst));
-    MRC(lv_upload(c, V.at, rawoff));
-    MCHK(c, V.tf.reserve((size_t)ntot * sizeof(float4)));
-    MCHK(c, V.sel.reserve((size_t)ntot * sizeof(float4)));
-    MCHK(c, V.flag.reserve((size_t)ntot * 4));
-    MCHK(c, V.pos.reserve((size_t)ntot * 4));
-    MCHK(c, V.seg.reserve((size_t)ntot * 4));
-    MCHK(c, V.selseg.reserve((size_t)ntot * 4));
-    MCHK(c, V.seloff.reserve((size_t)(nseg + 1) * 4));
-    MCHK(c, V.voxoff.reserve((size_t)(nseg + 1) * 4));
-    MCHK(c, V.tmp.reserve(std::max(prims::exclusive_sum_temp_bytes(ntot), prims::sort_temp_bytes(ntot))));
-    MCHK(c, V.reserve_host(std::max<size_t>((size_t)(nseg + 1) * 4, (size_t)L * sizeof(IcpDev))));
+    LISLAM_RC(lv_upload(c, V.T, V.hT));
+    LISLAM_RC(lv_upload(c, V.pieces, pc));
+    LISLAM_RC(lv_upload(c, V.pdst, pdst));
+    LISLAM_RC(lv_upload(c, V.at, rawoff));
+    LISLAM_HIPCHK(c, V.tf.reserve((size_t)ntot * sizeof(float4)));
+    LISLAM_HIPCHK(c, V.sel.reserve((size_t)ntot * sizeof(float4)));
+    LISLAM_HIPCHK(c, V.flag.reserve((size_t)ntot * 4));
+    LISLAM_HIPCHK(c, V.pos.reserve((size_t)ntot * 4));
+    LISLAM_HIPCHK(c, V.seg.reserve((size_t)ntot * 4));
+    LISLAM_HIPCHK(c, V.selseg.reserve((size_t)ntot * 4));
+    LISLAM_HIPCHK(c, V.seloff.reserve((size_t)(nseg + 1) * 4));
+    LISLAM_HIPCHK(c, V.voxoff.reserve((size_t)(nseg + 1) * 4));
+    LISLAM_HIPCHK(c, V.tmp.reserve(std::max(prims::exclusive_sum_temp_bytes(ntot), prims::sort_temp_bytes(ntot))));
+    LISLAM_HIPCHK(c, V.reserve_host(std::max<size_t>((size_t)(nseg + 1) * 4, (size_t)L * sizeof(IcpDev))));
     int* hoff = static_cast<int*>(V.host);
     // transform + removeNaN + CropBox
     hipLaunchKernelGGL(k_lv_transform, dim3(blocks(ntot)), dim3(256), 0, st, kf->pts, V.pieces.as<LvPiece>(),
                        V.pdst.as<int>(), (int)pc.size(), V.T.as<double>(), ntot, cfg->use_crop ? 1 : 0, -cfg->crop_size,
                        cfg->crop_size, V.tf.as<float4>(), V.flag.as<int>(), V.seg.as<int>());
-    MCHK(c, prims::exclusive_sum(V.tmp.p, V.flag.as<int>(), V.pos.as<int>(), ntot, st));
+    LISLAM_HIPCHK(c, prims::exclusive_sum(V.tmp.p, V.flag.as<int>(), V.pos.as<int>(), ntot, st));
     hipLaunchKernelGGL(k_lv_compact, dim3(blocks(ntot)), dim3(256), 0, st, V.tf.as<float4>(), V.flag.as<int>(),
                        V.pos.as<int>(), V.seg.as<int>(), ntot, V.sel.as<float4>(), V.selseg.as<int>());
     hipLaunchKernelGGL(k_lv_offsets, dim3(blocks(nseg + 1)), dim3(256), 0, st, V.pos.as<int>(), V.flag.as<int>(),
                        V.at.as<int>(), nseg + 1, ntot, V.seloff.as<int>());
-    MCHK(c, hipGetLastError());
-    MCHK(c, hipMemcpyAsync(hoff, V.seloff.p, (size_t)(nseg + 1) * 4, hipMemcpyDeviceToHost, st));
-    MCHK(c, hipStreamSynchronize(st));
+    LISLAM_HIPCHK(c, hipGetLastError());
+    LISLAM_HIPCHK(c, hipMemcpyAsync(hoff, V.seloff.p, (size_t)(nseg + 1) * 4, hipMemcpyDeviceToHost, st));
+    LISLAM_HIPCHK(c, hipStreamSynchronize(st));
     const int nsel = hoff[nseg];
     const float4* prepared = V.sel.as<float4>();  // the segments after filtering, back to back
     if (cfg->use_downsample && nsel > 0) {
       // VoxelGrid of every segment: out = V.tf (its points are all in V.sel by now)
-      MCHK(c, V.vx.reserve((size_t)nseg * sizeof(LvVox)));
-      MCHK(c, V.keys.reserve((size_t)nsel * 8));
-      MCHK(c, V.keys2.reserve((size_t)nsel * 8));
-      MCHK(c, V.idx.reserve((size_t)nsel * 4));
-      MCHK(c, V.idx2.reserve((size_t)nsel * 4));
+      LISLAM_HIPCHK(c, V.vx.reserve((size_t)nseg * sizeof(LvVox)));
+      LISLAM_HIPCHK(c, V.keys.reserve((size_t)nsel * 8));
+      LISLAM_HIPCHK(c, V.keys2.reserve((size_t)nsel * 8));
+      LISLAM_HIPCHK(c, V.idx.reserve((size_t)nsel * 4));
+      LISLAM_HIPCHK(c, V.idx2.reserve((size_t)nsel * 4));
       const float inv = 1.0f / cfg->voxel_size;
       hipLaunchKernelGGL(k_lv_bounds, dim3(nseg), dim3(1024), 0, st, prepared, V.seloff.as<int>(), inv, V.vx.as<LvVox>());
       hipLaunchKernelGGL(k_lv_keys, dim3(blocks(nsel)), dim3(256), 0, st, prepared, V.selseg.as<int>(), V.seloff.as<int>(),
                          V.vx.as<LvVox>(), inv, nsel, V.keys.as<uint64_t>(), V.idx.as<int>());
-      MCHK(c, prims::sort_pairs<uint64_t>(V.tmp.p, V.keys.as<uint64_t>(), V.keys2.as<uint64_t>(), V.idx.as<int>(),
-                                          V.idx2.as<int>(), nsel, 32 + lv_bits(nseg), st));
+      LISLAM_HIPCHK(c, prims::sort_pairs<uint64_t>(V.tmp.p, V.keys.as<uint64_t>(), V.keys2.as<uint64_t>(), V.idx.as<int>(),
+                                                   V.idx2.as<int>(), nsel, 32 + lv_bits(nseg), st));
       hipLaunchKernelGGL(k_lv_runs, dim3(blocks(nsel)), dim3(256), 0, st, V.keys2.as<uint64_t>(), nsel, V.flag.as<int>());
-      MCHK(c, prims::exclusive_sum(V.tmp.p, V.flag.as<int>(), V.pos.as<int>(), nsel, st));
+      LISLAM_HIPCHK(c, prims::exclusive_sum(V.tmp.p, V.flag.as<int>(), V.pos.as<int>(), nsel, st));
       hipLaunchKernelGGL(k_lv_centroids, dim3(blocks(nsel)), dim3(256), 0, st, prepared, V.keys2.as<uint64_t>(),
                          V.idx2.as<int>(), V.pos.as<int>(), V.flag.as<int>(), nsel, V.tf.as<float4>());
       hipLaunchKernelGGL(k_lv_offsets, dim3(blocks(nseg + 1)), dim3(256), 0, st, V.pos.as<int>(), V.flag.as<int>(),
                          V.seloff.as<int>(), nseg + 1, nsel, V.voxoff.as<int>());
-      MCHK(c, hipGetLastError());
-      MCHK(c, hipMemcpyAsync(hoff, V.voxoff.p, (size_t)(nseg + 1) * 4, hipMemcpyDeviceToHost, st));
-      MCHK(c, hipStreamSynchronize(st));
+      LISLAM_HIPCHK(c, hipGetLastError());
+      LISLAM_HIPCHK(c, hipMemcpyAsync(hoff, V.voxoff.p, (size_t)(nseg + 1) * 4, hipMemcpyDeviceToHost, st));
+      LISLAM_HIPCHK(c, hipStreamSynchronize(st));
       prepared = V.tf.as<float4>();
     }
     // the sizes decide who iterates
@@ -3554,27 +3502,27 @@ int lislam_loop_verify(lislam_keyframes* kf, const lislam_icp_config* cfg, int32
     if (na > 0) {
       std::vector<int> woff(na), toff(na);
       for (int a = 0; a < na; a++) { woff[a] = cd[a].w_off; toff[a] = cd[a].t_off; }
-      MRC(lv_upload(c, V.woff, woff));
-      MRC(lv_upload(c, V.toff, toff));
-      MRC(lv_upload(c, V.cand, cd));
-      MCHK(c, V.src.reserve((size_t)nw * sizeof(float4)));
-      MCHK(c, V.src0.reserve((size_t)nw * sizeof(float4)));
-      MCHK(c, V.ftf.reserve((size_t)nw * sizeof(float4)));
-      MCHK(c, V.nb.reserve((size_t)nw * sizeof(float4)));
-      MCHK(c, V.qseg.reserve((size_t)nw * 4));
-      MCHK(c, V.d2.reserve((size_t)nw * 4));
-      MCHK(c, V.found.reserve((size_t)nw * 4));
-      MCHK(c, V.tp.reserve((size_t)ntg * sizeof(float4)));
-      MCHK(c, V.tpts.reserve((size_t)ntg * sizeof(float4)));
-      MCHK(c, V.keys.reserve((size_t)ntg * 8));
-      MCHK(c, V.keys2.reserve((size_t)ntg * 8));
-      MCHK(c, V.ckey.reserve((size_t)ntg * 8));
-      MCHK(c, V.idx.reserve((size_t)ntg * 4));
-      MCHK(c, V.idx2.reserve((size_t)ntg * 4));
-      MCHK(c, V.owner.reserve((size_t)ntg * 4));
-      MCHK(c, V.owner2.reserve((size_t)ntg * 4));
-      MCHK(c, V.ncell.reserve((size_t)na * 4));
-      MCHK(c, V.tmp.reserve(prims::sort_temp_bytes(ntg)));
+      LISLAM_RC(lv_upload(c, V.woff, woff));
+      LISLAM_RC(lv_upload(c, V.toff, toff));
+      LISLAM_RC(lv_upload(c, V.cand, cd));
+      LISLAM_HIPCHK(c, V.src.reserve((size_t)nw * sizeof(float4)));
+      LISLAM_HIPCHK(c, V.src0.reserve((size_t)nw * sizeof(float4)));
+      LISLAM_HIPCHK(c, V.ftf.reserve((size_t)nw * sizeof(float4)));
+      LISLAM_HIPCHK(c, V.nb.reserve((size_t)nw * sizeof(float4)));
+      LISLAM_HIPCHK(c, V.qseg.reserve((size_t)nw * 4));
+      LISLAM_HIPCHK(c, V.d2.reserve((size_t)nw * 4));
+      LISLAM_HIPCHK(c, V.found.reserve((size_t)nw * 4));
+      LISLAM_HIPCHK(c, V.tp.reserve((size_t)ntg * sizeof(float4)));
+      LISLAM_HIPCHK(c, V.tpts.reserve((size_t)ntg * sizeof(float4)));
+      LISLAM_HIPCHK(c, V.keys.reserve((size_t)ntg * 8));
+      LISLAM_HIPCHK(c, V.keys2.reserve((size_t)ntg * 8));
+      LISLAM_HIPCHK(c, V.ckey.reserve((size_t)ntg * 8));
+      LISLAM_HIPCHK(c, V.idx.reserve((size_t)ntg * 4));
+      LISLAM_HIPCHK(c, V.idx2.reserve((size_t)ntg * 4));
+      LISLAM_HIPCHK(c, V.owner.reserve((size_t)ntg * 4));
+      LISLAM_HIPCHK(c, V.owner2.reserve((size_t)ntg * 4));
+      LISLAM_HIPCHK(c, V.ncell.reserve((size_t)na * 4));
+      LISLAM_HIPCHK(c, V.tmp.reserve(prims::sort_temp_bytes(ntg)));
       const float cell = std::max(1.0f, cfg->use_downsample ? 2.0f * cfg->voxel_size : 1.0f);
       const float inv_cell = 1.0f / cell;
       hipLaunchKernelGGL(k_lv_src, dim3(blocks(nw)), dim3(256), 0, st, prepared, V.cand.as<LvCand>(), V.woff.as<int>(), na, nw,
@@ -3585,36 +3533,36 @@ int lislam_loop_verify(lislam_keyframes* kf, const lislam_icp_config* cfg, int32
         TimedScope ts(c, kT_rebuild);
         hipLaunchKernelGGL(k_lv_tgt, dim3(blocks(ntg)), dim3(256), 0, st, prepared, V.cand.as<LvCand>(), V.toff.as<int>(), na,
                            ntg, inv_cell, V.tp.as<float4>(), V.keys.as<uint64_t>(), V.idx.as<int>());
-        MCHK(c, prims::sort_pairs<uint64_t>(V.tmp.p, V.keys.as<uint64_t>(), V.keys2.as<uint64_t>(), V.idx.as<int>(),
-                                            V.idx2.as<int>(), ntg, 64, st));
+        LISLAM_HIPCHK(c, prims::sort_pairs<uint64_t>(V.tmp.p, V.keys.as<uint64_t>(), V.keys2.as<uint64_t>(), V.idx.as<int>(),
+                                                     V.idx2.as<int>(), ntg, 64, st));
         const int* perm = V.idx2.as<int>();
         if (na > 1) {
           hipLaunchKernelGGL(k_lv_owner, dim3(blocks(ntg)), dim3(256), 0, st, V.idx2.as<int>(), V.toff.as<int>(), na, ntg,
                              V.owner.as<uint32_t>());
-          MCHK(c, prims::sort_pairs<uint32_t>(V.tmp.p, V.owner.as<uint32_t>(), V.owner2.as<uint32_t>(), V.idx2.as<int>(),
-                                              V.idx.as<int>(), ntg, lv_bits(na), st));
+          LISLAM_HIPCHK(c, prims::sort_pairs<uint32_t>(V.tmp.p, V.owner.as<uint32_t>(), V.owner2.as<uint32_t>(), V.idx2.as<int>(),
+                                                       V.idx.as<int>(), ntg, lv_bits(na), st));
           perm = V.idx.as<int>();
         }
         hipLaunchKernelGGL(k_lv_tgather, dim3(blocks(ntg)), dim3(256), 0, st, V.tp.as<float4>(), perm, ntg, inv_cell,
                            V.tpts.as<float4>(), V.ckey.as<uint64_t>());
-        MCHK(c, hipMemsetAsync(V.ncell.p, 0, (size_t)na * 4, st));
+        LISLAM_HIPCHK(c, hipMemsetAsync(V.ncell.p, 0, (size_t)na * 4, st));
         hipLaunchKernelGGL(k_lv_count_cells, dim3(blocks(ntg)), dim3(256), 0, st, V.ckey.as<uint64_t>(), V.toff.as<int>(), na,
                            ntg, V.ncell.as<int>());
-        MCHK(c, hipGetLastError());
-        MCHK(c, hipMemcpyAsync(hcell, V.ncell.p, (size_t)na * 4, hipMemcpyDeviceToHost, st));
-        MCHK(c, hipStreamSynchronize(st));
+        LISLAM_HIPCHK(c, hipGetLastError());
+        LISLAM_HIPCHK(c, hipMemcpyAsync(hcell, V.ncell.p, (size_t)na * 4, hipMemcpyDeviceToHost, st));
+        LISLAM_HIPCHK(c, hipStreamSynchronize(st));
         int64_t htot = 0;
         for (int a = 0; a < na; a++) {
           const uint32_t cap = pow2_at_least((uint64_t)hcell[a] * 2);
           cd[a].h_off = (int)htot;
           cd[a].hmask = cap - 1;
           htot += cap;
-          if (htot > 0x7fffffff) return mfail(c, LISLAM_ERR_CAPACITY, "lislam_loop_verify: the cell tables are too large");
+          if (htot > 0x7fffffff) return fail(c, LISLAM_ERR_CAPACITY, "lislam_loop_verify: the cell tables are too large");
         }
-        MRC(lv_upload(c, V.cand, cd));
-        MCHK(c, V.hkey.reserve((size_t)htot * 8));
-        MCHK(c, V.hval.reserve((size_t)htot * 8));
-        MCHK(c, hipMemsetAsync(V.hkey.p, 0xff, (size_t)htot * 8, st));
+        LISLAM_RC(lv_upload(c, V.cand, cd));
+        LISLAM_HIPCHK(c, V.hkey.reserve((size_t)htot * 8));
+        LISLAM_HIPCHK(c, V.hval.reserve((size_t)htot * 8));
+        LISLAM_HIPCHK(c, hipMemsetAsync(V.hkey.p, 0xff, (size_t)htot * 8, st));
         hipLaunchKernelGGL(k_lv_insert, dim3(blocks(ntg)), dim3(256), 0, st, V.ckey.as<uint64_t>(), V.cand.as<LvCand>(),
                            V.toff.as<int>(), na, ntg, V.hkey.as<uint64_t>(), V.hval.as<int2>());
       }
@@ -3631,7 +3579,7 @@ int lislam_loop_verify(lislam_keyframes* kf, const lislam_icp_config* cfg, int32
         v.scan_shell = mapk::scan_shell_for(cd[a].nt);
         v.near2 = mapk::knn_near2(cell);
       }
-      MRC(lv_upload(c, V.views, views));
+      LISLAM_RC(lv_upload(c, V.views, views));
       // ICP states
       hst = static_cast<IcpDev*>(V.host);
       std::memset(hst, 0, (size_t)na * sizeof(IcpDev));
@@ -3640,9 +3588,9 @@ int lislam_loop_verify(lislam_keyframes* kf, const lislam_icp_config* cfg, int32
         hst[a].prev_mse = DBL_MAX;
         hst[a].nq = cd[a].ns;
       }
-      MCHK(c, V.st.reserve((size_t)na * sizeof(IcpDev)));
+      LISLAM_HIPCHK(c, V.st.reserve((size_t)na * sizeof(IcpDev)));
       IcpDev* d = V.st.as<IcpDev>();
-      MCHK(c, hipMemcpyAsync(d, hst, (size_t)na * sizeof(IcpDev), hipMemcpyHostToDevice, st));
+      LISLAM_HIPCHK(c, hipMemcpyAsync(d, hst, (size_t)na * sizeof(IcpDev), hipMemcpyHostToDevice, st));
       IcpParams P;
       P.max_iter = cfg->max_iterations;
       P.rot_thr = 1.0 - cfg->transformation_epsilon;
@@ -3669,13 +3617,13 @@ int lislam_loop_verify(lislam_keyframes* kf, const lislam_icp_config* cfg, int32
           TimedScope ts(c, kT_icp_apply);
           hipLaunchKernelGGL(k_lv_apply, dim3(blocks(nw)), dim3(256), 0, st, d, V.qseg.as<int>(), V.src.as<float4>(), nw);
         }
-        MCHK(c, hipGetLastError());
-        MCHK(c, hipMemcpyAsync(hst, d, (size_t)na * sizeof(IcpDev), hipMemcpyDeviceToHost, st));
-        MCHK(c, hipStreamSynchronize(st));
+        LISLAM_HIPCHK(c, hipGetLastError());
+        LISLAM_HIPCHK(c, hipMemcpyAsync(hst, d, (size_t)na * sizeof(IcpDev), hipMemcpyDeviceToHost, st));
+        LISLAM_HIPCHK(c, hipStreamSynchronize(st));
         all_done = true;
         for (int a = 0; a < na; a++) all_done = all_done && hst[a].done;
       }
-      if (!all_done) return mfail(c, LISLAM_ERR_STATE, "lislam_loop_verify: iteration loop did not terminate");
+      if (!all_done) return fail(c, LISLAM_ERR_STATE, "lislam_loop_verify: iteration loop did not terminate");
       // fitness
       hipLaunchKernelGGL(k_lv_final_tf, dim3(blocks(nw)), dim3(256), 0, st, d, V.qseg.as<int>(), V.src0.as<float4>(), nw,
                          V.ftf.as<float4>());
@@ -3686,9 +3634,9 @@ int lislam_loop_verify(lislam_keyframes* kf, const lislam_icp_config* cfg, int32
       }
       hipLaunchKernelGGL(k_lv_fitness, dim3(na), dim3(kRed), 0, st, d, V.cand.as<LvCand>(), V.d2.as<float>(),
                          V.found.as<int>());
-      MCHK(c, hipGetLastError());
-      MCHK(c, hipMemcpyAsync(hst, d, (size_t)na * sizeof(IcpDev), hipMemcpyDeviceToHost, st));
-      MCHK(c, hipStreamSynchronize(st));
+      LISLAM_HIPCHK(c, hipGetLastError());
+      LISLAM_HIPCHK(c, hipMemcpyAsync(hst, d, (size_t)na * sizeof(IcpDev), hipMemcpyDeviceToHost, st));
+      LISLAM_HIPCHK(c, hipStreamSynchronize(st));
     }
   }
   // results
@@ -3846,7 +3794,7 @@ int lislam_odom_fuser_create(lislam_ctx* c, lislam_odom_fuser** out) {
   if (f->state.reserve(49 * 8) != hipSuccess || hipMemsetAsync(f->state.p, 0, 49 * 8, c->stream) != hipSuccess ||
       hipStreamSynchronize(c->stream) != hipSuccess) {
     delete f;
-    return mfail(c, LISLAM_ERR_DEVICE, "lislam_odom_fuser_create: allocation failed");
+    return fail(c, LISLAM_ERR_DEVICE, "lislam_odom_fuser_create: allocation failed");
   }
   *out = f;
   return LISLAM_OK;
@@ -3868,22 +3816,22 @@ int lislam_odom_fuse(lislam_odom_fuser* f, const double* aloam, const double* in
   hipSetDevice(c->device);
   hipStream_t st = c->stream;
   const size_t pb = (size_t)n * 7 * 8;
-  MCHK(c, f->io.reserve(3 * pb + (size_t)n * 4));
+  LISLAM_HIPCHK(c, f->io.reserve(3 * pb + (size_t)n * 4));
   char* base = f->io.as<char>();
   double* da = reinterpret_cast<double*>(base);
   double* di = reinterpret_cast<double*>(base + pb);
   double* dout = reinterpret_cast<double*>(base + 2 * pb);
   int* ds = reinterpret_cast<int*>(base + 3 * pb);
-  MCHK(c, hipMemcpyAsync(da, aloam, pb, hipMemcpyDefault, st));
-  MCHK(c, hipMemcpyAsync(di, intensity, pb, hipMemcpyDefault, st));
-  MCHK(c, hipMemcpyAsync(ds, skip, (size_t)n * 4, hipMemcpyDefault, st));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(da, aloam, pb, hipMemcpyDefault, st));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(di, intensity, pb, hipMemcpyDefault, st));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(ds, skip, (size_t)n * 4, hipMemcpyDefault, st));
   {
     TimedScope ts(c, kT_fuse);
     hipLaunchKernelGGL(lislam::fusek::k_fuse, dim3(1), dim3(64), 0, st, f->state.as<double>(), da, di, ds, n, dout);
   }
-  MCHK(c, hipGetLastError());
-  MCHK(c, hipMemcpyAsync(fused, dout, pb, hipMemcpyDefault, st));
-  MCHK(c, hipStreamSynchronize(st));
+  LISLAM_HIPCHK(c, hipGetLastError());
+  LISLAM_HIPCHK(c, hipMemcpyAsync(fused, dout, pb, hipMemcpyDefault, st));
+  LISLAM_HIPCHK(c, hipStreamSynchronize(st));
   return LISLAM_OK;
 }
 

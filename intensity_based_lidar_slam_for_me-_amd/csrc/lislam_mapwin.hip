@@ -23,11 +23,13 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <climits>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
 
 #include "lislam_device.hpp"
+#include "lislam_host.hpp"
 #include "lislam_mapwin.hpp"
 
 namespace lislam {
@@ -210,6 +212,7 @@ __global__ void k_mw_append(const double* prec, const int* pkind, const int* nco
 
 // ================================================================== host side
 using namespace lislam::mapwin;
+using namespace lislam;
 
 struct lislam_mapwin {
   lislam_ctx* ctx = nullptr;
@@ -222,9 +225,10 @@ struct lislam_mapwin {
   double* pose = nullptr;
   unsigned long long* best = nullptr;
   int2* sel = nullptr;
-  int *info = nullptr, *pairs = nullptr, *total = nullptr, *kind = nullptr;
-  double* rec = nullptr;
-  int rec_rows = 0;  // rows of rec / kind
+  int *info = nullptr, *pairs = nullptr, *total = nullptr;
+  DBuf rec, kind;  // records of 9 doubles, their kinds
+  // rows both buffers hold: read from the buffers, so a failed reallocation leaves 0
+  int rec_rows() const { return (int)std::min<size_t>(std::min(rec.bytes / 72, kind.bytes / 4), INT_MAX); }
   int free_slot() const { return (head + count) % slots; }
   int frec() const { return std::max(W, 1) * kMaxKeep; }
   View view() const {
@@ -240,45 +244,12 @@ struct lislam_mapwin {
 
 namespace {
 
-int wfail(lislam_ctx* c, int code, const char* fmt, ...) {
-  if (c) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    c->err = buf;
-  }
-  return code;
-}
-
-#define WCHK(ctx, x)                                                                              \
-  do {                                                                                            \
-    hipError_t e_ = (x);                                                                          \
-    if (e_ != hipSuccess) return wfail(ctx, LISLAM_ERR_DEVICE, "%s: %s", #x, hipGetErrorString(e_)); \
-  } while (0)
-
-#define WRC(x)                        \
-  do {                                \
-    int rc_ = (x);                    \
-    if (rc_ != LISLAM_OK) return rc_; \
-  } while (0)
-
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
 int reserve_records(lislam_mapwin* w, int rows) {
-  if (rows <= w->rec_rows) return LISLAM_OK;
   lislam_ctx* c = w->ctx;
-  WCHK(c, hipStreamSynchronize(c->stream));  // nothing in flight reads the old buffers
-  if (w->rec) (void)hipFree(w->rec);
-  if (w->kind) (void)hipFree(w->kind);
-  w->rec = nullptr;
-  w->kind = nullptr;
-  w->rec_rows = 0;
-  const int nr = rows + rows / 4;
-  WCHK(c, hipMalloc(&w->rec, (size_t)nr * 72));
-  WCHK(c, hipMalloc(&w->kind, (size_t)nr * 4));
-  w->rec_rows = nr;
+  LISLAM_HIPCHK(c, w->rec.reserve((size_t)rows * 72, c->stream));
+  LISLAM_HIPCHK(c, w->kind.reserve((size_t)rows * 4, c->stream));
   return LISLAM_OK;
 }
 
@@ -287,14 +258,14 @@ int match_device(lislam_mapwin* w) {
   lislam_ctx* c = w->ctx;
   const View v = w->view();
   if (v.nw == 0 || v.nq == 0) return LISLAM_OK;
-  WCHK(c, hipMemsetAsync(w->best, 0xff, (size_t)v.nw * w->cap * 8, c->stream));
+  LISLAM_HIPCHK(c, hipMemsetAsync(w->best, 0xff, (size_t)v.nw * w->cap * 8, c->stream));
   int mt = 0;
   for (int i = 0; i < v.nw; i++) mt = std::max(mt, v.nt[i]);
   if (mt > 0) {
     TimedScope ts(c, kT_mw_match);
     hipLaunchKernelGGL(k_mw_match, dim3(cdiv(v.nq, kQTile), cdiv(mt, kTTile), v.nw), dim3(kTTile), 0, c->stream, v, w->best);
   }
-  WCHK(c, hipGetLastError());
+  LISLAM_HIPCHK(c, hipGetLastError());
   return LISLAM_OK;
 }
 
@@ -306,8 +277,8 @@ namespace mapwin {
 lislam_ctx* context(lislam_mapwin* w) { return w->ctx; }
 int window_size(lislam_mapwin* w) { return w->W; }
 int feature_capacity(lislam_mapwin* w) { return w->cap; }
-double* rec(lislam_mapwin* w) { return w->rec; }
-int* kind(lislam_mapwin* w) { return w->kind; }
+double* rec(lislam_mapwin* w) { return w->rec.as<double>(); }
+int* kind(lislam_mapwin* w) { return w->kind.as<int>(); }
 int* total(lislam_mapwin* w) { return w->total; }
 int* info(lislam_mapwin* w) { return w->info; }
 int* pairs(lislam_mapwin* w) { return w->pairs; }
@@ -316,11 +287,11 @@ int capacity_records(lislam_mapwin* w) { return w->frec(); }
 int stage(lislam_mapwin* w, const uint8_t* desc, const float* p3d, int n) {
   lislam_ctx* c = w->ctx;
   if (n < 0 || (n > 0 && (!desc || !p3d))) return LISLAM_ERR_ARG;
-  if (n > w->cap) return wfail(c, LISLAM_ERR_CAPACITY, "lislam_mapwin: %d features > feature_capacity %d", n, w->cap);
+  if (n > w->cap) return fail(c, LISLAM_ERR_CAPACITY, "lislam_mapwin: %d features > feature_capacity %d", n, w->cap);
   if (n > 0 && desc != stage_desc(w))
-    WCHK(c, hipMemcpyAsync(stage_desc(w), desc, (size_t)n * 32, hipMemcpyDefault, c->stream));
+    LISLAM_HIPCHK(c, hipMemcpyAsync(stage_desc(w), desc, (size_t)n * 32, hipMemcpyDefault, c->stream));
   if (n > 0 && p3d != stage_p3d(w))
-    WCHK(c, hipMemcpyAsync(stage_p3d(w), p3d, (size_t)n * 16, hipMemcpyDefault, c->stream));
+    LISLAM_HIPCHK(c, hipMemcpyAsync(stage_p3d(w), p3d, (size_t)n * 16, hipMemcpyDefault, c->stream));
   w->staged = n;
   return LISLAM_OK;
 }
@@ -331,36 +302,37 @@ float* stage_p3d(lislam_mapwin* w) { return reinterpret_cast<float*>(w->p3d + (s
 int records(lislam_mapwin* w, const double* pose, int plane_cap) {
   lislam_ctx* c = w->ctx;
   hipStream_t st = c->stream;
-  WRC(reserve_records(w, w->frec() + std::max(plane_cap, 0)));
+  LISLAM_RC(reserve_records(w, w->frec() + std::max(plane_cap, 0)));
   const View v = w->view();
-  WCHK(c, hipMemsetAsync(w->info, 0, (size_t)(kMaxWindow * 6 + 2) * 4, st));
+  LISLAM_HIPCHK(c, hipMemsetAsync(w->info, 0, (size_t)(kMaxWindow * 6 + 2) * 4, st));
   if (v.nw == 0) return LISLAM_OK;
-  WRC(match_device(w));
+  LISLAM_RC(match_device(w));
   {
     TimedScope ts(c, kT_mw_select);
     hipLaunchKernelGGL(k_mw_select, dim3(v.nw), dim3(kSelThreads), 0, st, v, w->best, w->sel, w->info);
   }
   {
     TimedScope ts(c, kT_mw_gate);
-    hipLaunchKernelGGL(k_mw_gate, dim3(1), dim3(kGateThreads), 0, st, v, w->sel, pose, w->info, w->rec, w->kind, w->pairs);
+    hipLaunchKernelGGL(k_mw_gate, dim3(1), dim3(kGateThreads), 0, st, v, w->sel, pose, w->info, w->rec.as<double>(), w->kind.as<int>(),
+                       w->pairs);
   }
-  WCHK(c, hipGetLastError());
+  LISLAM_HIPCHK(c, hipGetLastError());
   return LISLAM_OK;
 }
 
 int append(lislam_mapwin* w, const double* prec, const int* pkind, const int* ncount, int n) {
   lislam_ctx* c = w->ctx;
-  if (w->frec() + n > w->rec_rows) return wfail(c, LISLAM_ERR_STATE, "lislam_mapwin: plane records beyond the reserved rows");
+  if (w->frec() + n > w->rec_rows()) return fail(c, LISLAM_ERR_STATE, "lislam_mapwin: plane records beyond the reserved rows");
   hipLaunchKernelGGL(k_mw_append, dim3(std::max(1, std::min(cdiv(n * 9, 256), 1024))), dim3(256), 0, c->stream, prec, pkind,
-                     ncount, n, w->info + w->count * 6, w->rec, w->kind, w->total);
-  WCHK(c, hipGetLastError());
+                     ncount, n, w->info + w->count * 6, w->rec.as<double>(), w->kind.as<int>(), w->total);
+  LISLAM_HIPCHK(c, hipGetLastError());
   return LISLAM_OK;
 }
 
 int push_staged(lislam_mapwin* w, const double* pose) {
   lislam_ctx* c = w->ctx;
   const int s = w->free_slot();
-  WCHK(c, hipMemcpyAsync(w->pose + (size_t)s * 8, pose, 56, hipMemcpyDefault, c->stream));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(w->pose + (size_t)s * 8, pose, 56, hipMemcpyDefault, c->stream));
   w->nslot[s] = w->staged;
   w->staged = 0;
   w->count++;
@@ -380,7 +352,7 @@ int lislam_mapwin_create(lislam_ctx* c, int32_t window_size, int32_t feature_cap
   if (!c || !out) return LISLAM_ERR_ARG;
   *out = nullptr;
   if (window_size < 0 || window_size > kMaxWindow || feature_capacity < 1 || feature_capacity > kMaxFeatures)
-    return wfail(c, LISLAM_ERR_ARG, "lislam_mapwin_create: window_size 0..%d, feature_capacity 1..%d", kMaxWindow, kMaxFeatures);
+    return fail(c, LISLAM_ERR_ARG, "lislam_mapwin_create: window_size 0..%d, feature_capacity 1..%d", kMaxWindow, kMaxFeatures);
   hipSetDevice(c->device);
   lislam_mapwin* w = new lislam_mapwin();
   w->ctx = c;
@@ -399,7 +371,7 @@ int lislam_mapwin_create(lislam_ctx* c, int32_t window_size, int32_t feature_cap
   if (e == hipSuccess) e = hipMemsetAsync(w->info, 0, (size_t)(kMaxWindow * 6 + 2) * 4, c->stream);
   if (e != hipSuccess) {
     lislam_mapwin_destroy(w);
-    return wfail(c, LISLAM_ERR_DEVICE, "lislam_mapwin_create: %s", hipGetErrorString(e));
+    return fail(c, LISLAM_ERR_DEVICE, "lislam_mapwin_create: %s", hipGetErrorString(e));
   }
   *out = w;
   return LISLAM_OK;
@@ -410,7 +382,7 @@ int lislam_mapwin_destroy(lislam_mapwin* w) {
   hipSetDevice(w->ctx->device);
   (void)hipStreamSynchronize(w->ctx->stream);
   for (void* p : {(void*)w->desc, (void*)w->p3d, (void*)w->pose, (void*)w->best, (void*)w->sel, (void*)w->info,
-                  (void*)w->pairs, (void*)w->total, (void*)w->kind, (void*)w->rec})
+                  (void*)w->pairs, (void*)w->total})
     if (p) (void)hipFree(p);
   delete w;
   return LISLAM_OK;
@@ -425,9 +397,9 @@ int lislam_mapwin_size(lislam_mapwin* w, int32_t* n) {
 int lislam_mapwin_push(lislam_mapwin* w, const uint8_t* desc, const float* p3d, int32_t n, const double* pose) {
   if (!w || !pose) return LISLAM_ERR_ARG;
   hipSetDevice(w->ctx->device);
-  WRC(stage(w, desc, p3d, n));
-  WRC(push_staged(w, pose));
-  WCHK(w->ctx, hipStreamSynchronize(w->ctx->stream));
+  LISLAM_RC(stage(w, desc, p3d, n));
+  LISLAM_RC(push_staged(w, pose));
+  LISLAM_HIPCHK(w->ctx, hipStreamSynchronize(w->ctx->stream));
   return LISLAM_OK;
 }
 
@@ -438,11 +410,11 @@ int lislam_mapwin_keyframe(lislam_mapwin* w, int32_t index, uint8_t* desc, float
   hipSetDevice(c->device);
   const int s = (w->head + index) % w->slots, cnt = w->nslot[s];
   *n = cnt;
-  if ((desc || p3d) && cnt > cap) return wfail(c, LISLAM_ERR_CAPACITY, "lislam_mapwin_keyframe: %d features > cap %d", cnt, cap);
-  if (desc && cnt) WCHK(c, hipMemcpyAsync(desc, w->desc + (size_t)s * w->cap * 32, (size_t)cnt * 32, hipMemcpyDefault, c->stream));
-  if (p3d && cnt) WCHK(c, hipMemcpyAsync(p3d, w->p3d + (size_t)s * w->cap, (size_t)cnt * 16, hipMemcpyDefault, c->stream));
-  if (pose) WCHK(c, hipMemcpyAsync(pose, w->pose + (size_t)s * 8, 56, hipMemcpyDefault, c->stream));
-  WCHK(c, hipStreamSynchronize(c->stream));
+  if ((desc || p3d) && cnt > cap) return fail(c, LISLAM_ERR_CAPACITY, "lislam_mapwin_keyframe: %d features > cap %d", cnt, cap);
+  if (desc && cnt) LISLAM_HIPCHK(c, hipMemcpyAsync(desc, w->desc + (size_t)s * w->cap * 32, (size_t)cnt * 32, hipMemcpyDefault, c->stream));
+  if (p3d && cnt) LISLAM_HIPCHK(c, hipMemcpyAsync(p3d, w->p3d + (size_t)s * w->cap, (size_t)cnt * 16, hipMemcpyDefault, c->stream));
+  if (pose) LISLAM_HIPCHK(c, hipMemcpyAsync(pose, w->pose + (size_t)s * 8, 56, hipMemcpyDefault, c->stream));
+  LISLAM_HIPCHK(c, hipStreamSynchronize(c->stream));
   return LISLAM_OK;
 }
 
@@ -450,14 +422,14 @@ int lislam_mapwin_match(lislam_mapwin* w, const uint8_t* desc, int32_t n, int32_
   if (!w || n < 0 || (n > 0 && !desc) || (n > 0 && w->count > 0 && !matches)) return LISLAM_ERR_ARG;
   lislam_ctx* c = w->ctx;
   hipSetDevice(c->device);
-  if (n > w->cap) return wfail(c, LISLAM_ERR_CAPACITY, "lislam_mapwin_match: %d features > feature_capacity %d", n, w->cap);
+  if (n > w->cap) return fail(c, LISLAM_ERR_CAPACITY, "lislam_mapwin_match: %d features > feature_capacity %d", n, w->cap);
   if (n == 0 || w->count == 0) return LISLAM_OK;
   hipStream_t st = c->stream;
-  WCHK(c, hipMemcpyAsync(w->desc + (size_t)w->free_slot() * w->cap * 32, desc, (size_t)n * 32, hipMemcpyDefault, st));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(w->desc + (size_t)w->free_slot() * w->cap * 32, desc, (size_t)n * 32, hipMemcpyDefault, st));
   w->staged = n;
-  WRC(match_device(w));
+  LISLAM_RC(match_device(w));
   int* dm = nullptr;
-  WCHK(c, hipMalloc(&dm, (size_t)w->count * n * 8));
+  LISLAM_HIPCHK(c, hipMalloc(&dm, (size_t)w->count * n * 8));
   const View v = w->view();
   hipLaunchKernelGGL(k_mw_export, dim3(cdiv(n, 256), v.nw), dim3(256), 0, st, v, w->best, dm);
   hipError_t e = hipGetLastError();
@@ -465,7 +437,7 @@ int lislam_mapwin_match(lislam_mapwin* w, const uint8_t* desc, int32_t n, int32_
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   (void)hipFree(dm);
   w->staged = 0;
-  WCHK(c, e);
+  LISLAM_HIPCHK(c, e);
   return LISLAM_OK;
 }
 
@@ -475,7 +447,7 @@ int lislam_mapwin_records(lislam_mapwin* w, const uint8_t* desc, const float* p3
   lislam_ctx* c = w->ctx;
   hipSetDevice(c->device);
   hipStream_t st = c->stream;
-  WRC(stage(w, desc, p3d, n));
+  LISLAM_RC(stage(w, desc, p3d, n));
   double* dpose = w->pose + (size_t)w->slots * 8;
   int hi[kMaxWindow * 6 + 2];
   hipError_t e = hipMemcpyAsync(dpose, pose, 56, hipMemcpyDefault, st);
@@ -483,17 +455,17 @@ int lislam_mapwin_records(lislam_mapwin* w, const uint8_t* desc, const float* p3
   if (e == hipSuccess && rc == LISLAM_OK) e = hipMemcpyAsync(hi, w->info, sizeof(hi), hipMemcpyDeviceToHost, st);
   if (e == hipSuccess) e = hipStreamSynchronize(st);
   w->staged = 0;
-  WCHK(c, e);
-  WRC(rc);
+  LISLAM_HIPCHK(c, e);
+  LISLAM_RC(rc);
   const int nr = hi[w->count * 6];
   *n_rec = nr;
   if (info)
     for (int i = 0; i < w->W * 6; i++) info[i] = i < w->count * 6 ? hi[i] : 0;
-  if (nr > cap) return wfail(c, LISLAM_ERR_CAPACITY, "lislam_mapwin_records: %d records > cap %d", nr, cap);
+  if (nr > cap) return fail(c, LISLAM_ERR_CAPACITY, "lislam_mapwin_records: %d records > cap %d", nr, cap);
   if (nr) {
-    WCHK(c, hipMemcpyAsync(rec, w->rec, (size_t)nr * 72, hipMemcpyDefault, st));
-    if (pairs) WCHK(c, hipMemcpyAsync(pairs, w->pairs, (size_t)nr * 12, hipMemcpyDefault, st));
-    WCHK(c, hipStreamSynchronize(st));
+    LISLAM_HIPCHK(c, hipMemcpyAsync(rec, w->rec.p, (size_t)nr * 72, hipMemcpyDefault, st));
+    if (pairs) LISLAM_HIPCHK(c, hipMemcpyAsync(pairs, w->pairs, (size_t)nr * 12, hipMemcpyDefault, st));
+    LISLAM_HIPCHK(c, hipStreamSynchronize(st));
   }
   return LISLAM_OK;
 }

@@ -52,6 +52,7 @@
 #include "lislam_batch.hpp"
 #include "lislam_ctx.hpp"
 #include "lislam_device.hpp"
+#include "lislam_host.hpp"
 #include "lislam_lm.hpp"
 
 namespace lislam {
@@ -1886,29 +1887,6 @@ using namespace lislam::orbk;
 
 namespace {
 
-int ofail(lislam_ctx* c, int code, const char* fmt, ...) {
-  if (c) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    c->err = buf;
-  }
-  return code;
-}
-
-#define OCHK(ctx, x)                                                                          \
-  do {                                                                                        \
-    hipError_t e_ = (x);                                                                      \
-    if (e_ != hipSuccess) return ofail(ctx, LISLAM_ERR_DEVICE, "%s: %s", #x, hipGetErrorString(e_)); \
-  } while (0)
-#define ORC(x)                        \
-  do {                                \
-    int rc_ = (x);                    \
-    if (rc_ != LISLAM_OK) return rc_; \
-  } while (0)
-
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 
 int cv_round(float v) { return (int)std::nearbyint(v); }
@@ -1951,7 +1929,7 @@ struct OrbEngine {
   int alloc(T** p, size_t count) {
     void* q = nullptr;
     hipError_t e = hipMalloc(&q, std::max<size_t>(count, 1) * sizeof(T));
-    if (e != hipSuccess) return ofail(ctx, LISLAM_ERR_DEVICE, "hipMalloc(%zu): %s", count * sizeof(T), hipGetErrorString(e));
+    if (e != hipSuccess) return fail(ctx, LISLAM_ERR_DEVICE, "hipMalloc(%zu): %s", count * sizeof(T), hipGetErrorString(e));
     allocs.push_back(q);
     *p = static_cast<T*>(q);
     return LISLAM_OK;
@@ -1987,7 +1965,7 @@ int engine_init(OrbEngine* e, lislam_ctx* c, int H, int W, int max_scans, int nf
     g.scale[l] = scale;
     g.w[l] = cv_round((float)W * inv);
     g.h[l] = cv_round((float)H * inv);
-    if (g.w[l] < 1 || g.h[l] < 1) return ofail(c, LISLAM_ERR_ARG, "image %dx%d too small for 8 ORB levels", W, H);
+    if (g.w[l] < 1 || g.h[l] < 1) return fail(c, LISLAM_ERR_ARG, "image %dx%d too small for 8 ORB levels", W, H);
     g.stride[l] = (g.w[l] + 2 * kB + 15) & ~15;  // 16-byte aligned rows (staged as dwords)
     g.off[l] = off;
     off += g.stride[l] * (g.h[l] + 2 * kB);
@@ -1997,7 +1975,7 @@ int engine_init(OrbEngine* e, lislam_ctx* c, int H, int W, int max_scans, int nf
     g.lofs[l + 1] = g.lofs[l] + g.lcap[l];
   }
   if ((kFastBand + 2) * (g.w[0] + 2) > 65536)  // k_orb_fastnms' u16 candidate list
-    return ofail(c, LISLAM_ERR_ARG, "image width %d too large for the FAST band", W);
+    return fail(c, LISLAM_ERR_ARG, "image width %d too large for the FAST band", W);
   g.fband[0] = 0;
   g.bband[0] = 0;
   g.rband[0] = 0;
@@ -2032,9 +2010,9 @@ int engine_init(OrbEngine* e, lislam_ctx* c, int H, int W, int max_scans, int nf
     for (int v = -kHalf; v <= kHalf; v++)
       for (int u = -umax[std::abs(v)]; u <= umax[std::abs(v)]; u++) patch.push_back(make_short2((short)u, (short)v));
     g.npatch = (int)patch.size();
-    if (g.npatch != kNPatch) return ofail(c, LISLAM_ERR_STATE, "ICAngles patch has %d pixels", g.npatch);
-    OCHK(c, hipMemcpyToSymbolAsync(HIP_SYMBOL(c_patch), patch.data(), patch.size() * sizeof(short2), 0,
-                                   hipMemcpyHostToDevice, c->stream));
+    if (g.npatch != kNPatch) return fail(c, LISLAM_ERR_STATE, "ICAngles patch has %d pixels", g.npatch);
+    LISLAM_HIPCHK(c, hipMemcpyToSymbolAsync(HIP_SYMBOL(c_patch), patch.data(), patch.size() * sizeof(short2), 0,
+                                            hipMemcpyHostToDevice, c->stream));
   }
   // resize tables (INTER_LINEAR_EXACT of level l from level l-1)
   e->xs = g.w[0];
@@ -2069,41 +2047,41 @@ int engine_init(OrbEngine* e, lislam_ctx* c, int H, int W, int max_scans, int nf
     }
   }
   hipStream_t st = c->stream;
-  ORC(e->alloc(&e->xo, hxo.size()));
-  ORC(e->alloc(&e->yo, hyo.size()));
-  ORC(e->alloc(&e->xc, hxc.size()));
-  ORC(e->alloc(&e->yc, hyc.size()));
-  ORC(e->alloc(&e->lim, hlim.size()));
-  OCHK(c, hipMemcpyAsync(e->xo, hxo.data(), hxo.size() * 4, hipMemcpyHostToDevice, st));
-  OCHK(c, hipMemcpyAsync(e->yo, hyo.data(), hyo.size() * 4, hipMemcpyHostToDevice, st));
-  OCHK(c, hipMemcpyAsync(e->xc, hxc.data(), hxc.size() * 2, hipMemcpyHostToDevice, st));
-  OCHK(c, hipMemcpyAsync(e->yc, hyc.data(), hyc.size() * 2, hipMemcpyHostToDevice, st));
-  OCHK(c, hipMemcpyAsync(e->lim, hlim.data(), hlim.size() * 4, hipMemcpyHostToDevice, st));
+  LISLAM_RC(e->alloc(&e->xo, hxo.size()));
+  LISLAM_RC(e->alloc(&e->yo, hyo.size()));
+  LISLAM_RC(e->alloc(&e->xc, hxc.size()));
+  LISLAM_RC(e->alloc(&e->yc, hyc.size()));
+  LISLAM_RC(e->alloc(&e->lim, hlim.size()));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(e->xo, hxo.data(), hxo.size() * 4, hipMemcpyHostToDevice, st));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(e->yo, hyo.data(), hyo.size() * 4, hipMemcpyHostToDevice, st));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(e->xc, hxc.data(), hxc.size() * 2, hipMemcpyHostToDevice, st));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(e->yc, hyc.data(), hyc.size() * 2, hipMemcpyHostToDevice, st));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(e->lim, hlim.data(), hlim.size() * 4, hipMemcpyHostToDevice, st));
   const size_t S = max_scans;
-  ORC(e->alloc(&e->pyr, S * g.bytes));
-  ORC(e->alloc(&e->blur, S * g.bytes));
-  ORC(e->alloc(&e->nms, S * g.pix[kL] + 16));  // + 16: k_orb_select reads whole aligned dwords
-  ORC(e->alloc(&e->cand, S * g.pix[kL]));
-  ORC(e->alloc(&e->cresp, S * g.pix[kL]));
-  ORC(e->alloc(&e->lkp, S * g.cap * 6));
-  ORC(e->alloc(&e->lcnt, S * kL));
-  ORC(e->alloc(&e->kp, S * g.cap * 6));
-  ORC(e->alloc(&e->p3d, S * g.cap));
-  ORC(e->alloc(&e->desc, S * g.cap * 32));
-  ORC(e->alloc(&e->nkp, S));
-  ORC(e->alloc(&e->overflow, 1));
-  ORC(e->alloc(&e->smap, S));
-  OCHK(c, hipMemsetAsync(e->overflow, 0, 4, st));
+  LISLAM_RC(e->alloc(&e->pyr, S * g.bytes));
+  LISLAM_RC(e->alloc(&e->blur, S * g.bytes));
+  LISLAM_RC(e->alloc(&e->nms, S * g.pix[kL] + 16));  // + 16: k_orb_select reads whole aligned dwords
+  LISLAM_RC(e->alloc(&e->cand, S * g.pix[kL]));
+  LISLAM_RC(e->alloc(&e->cresp, S * g.pix[kL]));
+  LISLAM_RC(e->alloc(&e->lkp, S * g.cap * 6));
+  LISLAM_RC(e->alloc(&e->lcnt, S * kL));
+  LISLAM_RC(e->alloc(&e->kp, S * g.cap * 6));
+  LISLAM_RC(e->alloc(&e->p3d, S * g.cap));
+  LISLAM_RC(e->alloc(&e->desc, S * g.cap * 32));
+  LISLAM_RC(e->alloc(&e->nkp, S));
+  LISLAM_RC(e->alloc(&e->overflow, 1));
+  LISLAM_RC(e->alloc(&e->smap, S));
+  LISLAM_HIPCHK(c, hipMemsetAsync(e->overflow, 0, 4, st));
   if (mask) {  // mask pyramid, once
     uint8_t* dmask = nullptr;
-    ORC(e->alloc(&dmask, (size_t)H * W));
-    ORC(e->alloc(&e->mpyr, g.bytes));
-    OCHK(c, hipMemcpyAsync(dmask, mask, (size_t)H * W, hipMemcpyDefault, st));
+    LISLAM_RC(e->alloc(&dmask, (size_t)H * W));
+    LISLAM_RC(e->alloc(&e->mpyr, g.bytes));
+    LISLAM_HIPCHK(c, hipMemcpyAsync(dmask, mask, (size_t)H * W, hipMemcpyDefault, st));
     Args a = e->args(dmask, nullptr);
     for (int l = 0; l < kL; l++)
       hipLaunchKernelGGL(k_orb_level, dim3(cdiv(g.stride[l] * (g.h[l] + 2 * kB), 256 * kLevelPx), 1), dim3(256), 0, st,
                          a, l, 1);
-    OCHK(c, hipGetLastError());
+    LISLAM_HIPCHK(c, hipGetLastError());
   }
   return LISLAM_OK;
 }
@@ -2142,7 +2120,7 @@ int engine_detect_slots(OrbEngine* e, const uint8_t* d_img, const float4* d_trac
   Args a = list ? e->args(d_img, d_track) : args_slot(e, d_img, d_track, slot0);
   a.S = n;
   if (list) {
-    OCHK(c, hipMemcpyAsync(e->smap, list, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    LISLAM_HIPCHK(c, hipMemcpyAsync(e->smap, list, (size_t)n * 4, hipMemcpyHostToDevice, st));
     a.smap = e->smap;
   }
   const Geom& g = e->g;
@@ -2177,7 +2155,7 @@ int engine_detect_slots(OrbEngine* e, const uint8_t* d_img, const float4* d_trac
     hipLaunchKernelGGL(k_orb_blur, dim3(g.bband[kL], n), dim3(256), (size_t)(kBlurBand + 6) * g.stride[0], st, a);
   }
   { TimedScope t(c, kT_orb_desc); hipLaunchKernelGGL(k_orb_desc, dim3(cdiv(g.cap, kDescChunk), n), dim3(256), 0, st, a); }
-  OCHK(c, hipGetLastError());
+  LISLAM_HIPCHK(c, hipGetLastError());
   return LISLAM_OK;
 }
 
@@ -2206,7 +2184,7 @@ int engine_select_from(OrbEngine* e, const OrbEngine* src, const uint8_t* d_img,
   { TimedScope t(c, kT_orb_select); hipLaunchKernelGGL(k_orb_select_list, dim3(ns * kL), dim3(kSelThreads), 0, st, a); }
   { TimedScope t(c, kT_orb_finish); hipLaunchKernelGGL(k_orb_finish, dim3(ns), dim3(256), 0, st, a); }
   { TimedScope t(c, kT_orb_desc); hipLaunchKernelGGL(k_orb_desc, dim3(cdiv(g.cap, kDescChunk), ns), dim3(256), 0, st, a); }
-  OCHK(c, hipGetLastError());
+  LISLAM_HIPCHK(c, hipGetLastError());
   return LISLAM_OK;
 }
 
@@ -2226,28 +2204,28 @@ struct PairBufs {
   int alloc(T_** p, size_t count) {
     void* q = nullptr;
     hipError_t e = hipMalloc(&q, std::max<size_t>(count, 1) * sizeof(T_));
-    if (e != hipSuccess) return ofail(ctx, LISLAM_ERR_DEVICE, "hipMalloc(%zu): %s", count * sizeof(T_), hipGetErrorString(e));
+    if (e != hipSuccess) return fail(ctx, LISLAM_ERR_DEVICE, "hipMalloc(%zu): %s", count * sizeof(T_), hipGetErrorString(e));
     allocs.push_back(q);
     *p = static_cast<T_*>(q);
     return LISLAM_OK;
   }
   int init(lislam_ctx* c, int maxp_, int qcap_, bool raw) {
     ctx = c; maxp = maxp_; qcap = qcap_;
-    ORC(alloc(&args, (size_t)3 * maxp));
-    ORC(alloc(&redet, maxp));
-    ORC(alloc(&mscratch, (size_t)maxp * qcap));
+    LISLAM_RC(alloc(&args, (size_t)3 * maxp));
+    LISLAM_RC(alloc(&redet, maxp));
+    LISLAM_RC(alloc(&mscratch, (size_t)maxp * qcap));
     // the best[] rows start at the "no match" sentinel; k_orb_match puts back each row it consumed
     if (hipMemset(mscratch, 0x7f, (size_t)maxp * qcap * sizeof(int)) != hipSuccess)
-      return ofail(ctx, LISLAM_ERR_DEVICE, "hipMemset of the match rows failed");
-    ORC(alloc(&arrive, maxp + 1));  // k_orb_pairs' arrival counters and k_orb_lm's, 0 between launches
+      return fail(ctx, LISLAM_ERR_DEVICE, "hipMemset of the match rows failed");
+    LISLAM_RC(alloc(&arrive, maxp + 1));  // k_orb_pairs' arrival counters and k_orb_lm's, 0 between launches
     tail_arrive = arrive + maxp;
     if (hipMemset(arrive, 0, (size_t)(maxp + 1) * sizeof(int)) != hipSuccess)
-      return ofail(ctx, LISLAM_ERR_DEVICE, "hipMemset of the pair arrival counters failed");
-    if (raw) ORC(alloc(&mout, (size_t)maxp * qcap * 3));
-    ORC(alloc(&kind, (size_t)maxp * qcap));
-    ORC(alloc(&stats, (size_t)maxp * 8));
-    ORC(alloc(&rec, (size_t)maxp * qcap * 9));
-    ORC(alloc(&T, (size_t)maxp * 7));
+      return fail(ctx, LISLAM_ERR_DEVICE, "hipMemset of the pair arrival counters failed");
+    if (raw) LISLAM_RC(alloc(&mout, (size_t)maxp * qcap * 3));
+    LISLAM_RC(alloc(&kind, (size_t)maxp * qcap));
+    LISLAM_RC(alloc(&stats, (size_t)maxp * 8));
+    LISLAM_RC(alloc(&rec, (size_t)maxp * qcap * 9));
+    LISLAM_RC(alloc(&T, (size_t)maxp * 7));
     return LISLAM_OK;
   }
 };
@@ -2270,11 +2248,11 @@ int run_pairs(lislam_ctx* c, const OrbEngine* qe, const OrbEngine* te, const int
   }
   if (n <= 0) {
     if (tl.kind) hipLaunchKernelGGL(k_orb_tail, dim3(1), dim3(256), 0, st, tl);
-    OCHK(c, hipGetLastError());
+    LISLAM_HIPCHK(c, hipGetLastError());
     return LISLAM_OK;
   }
   if (qe->g.cap > pb.qcap || (!slots && !dlist && p0 + n > pb.maxp) || n > pb.maxp)
-    return ofail(c, LISLAM_ERR_CAPACITY, "pair buffers too small");
+    return fail(c, LISLAM_ERR_CAPACITY, "pair buffers too small");
   PairArgs p;
   p.npairs = n;
   p.pcount = dcount;
@@ -2287,7 +2265,7 @@ int run_pairs(lislam_ctx* c, const OrbEngine* qe, const OrbEngine* te, const int
     std::copy(qs, qs + n, host.begin());
     std::copy(ts, ts + n, host.begin() + n);
     if (slots) std::copy(slots, slots + n, host.begin() + 2 * n);
-    OCHK(c, hipMemcpyAsync(pb.args, host.data(), (size_t)(slots ? 3 : 2) * n * 4, hipMemcpyHostToDevice, st));
+    LISLAM_HIPCHK(c, hipMemcpyAsync(pb.args, host.data(), (size_t)(slots ? 3 : 2) * n * 4, hipMemcpyHostToDevice, st));
     p.pslot = slots ? pb.args + 2 * n : nullptr;
     p.qscan = pb.args; p.tscan = pb.args + n;
   }
@@ -2324,7 +2302,7 @@ int run_pairs(lislam_ctx* c, const OrbEngine* qe, const OrbEngine* te, const int
   } else if (tl.kind) {
     hipLaunchKernelGGL(k_orb_tail, dim3(1), dim3(256), 0, st, tl);
   }
-  OCHK(c, hipGetLastError());
+  LISLAM_HIPCHK(c, hipGetLastError());
   return LISLAM_OK;
 }
 
@@ -2391,8 +2369,8 @@ int orb_batch_get(lislam_batch* b, int nfeatures, const uint8_t* mask, OrbBatch*
     ob->e1 = new OrbEngine();
     ob->e2 = new OrbEngine();
     static const bool own_side = getenv("LISLAM_ORB_SIDE_STREAM") && atoi(getenv("LISLAM_ORB_SIDE_STREAM")) == 1;
-    if (own_side && !work_stream(c->device, &ob->side)) return ofail(c, LISLAM_ERR_DEVICE, "ORB stream");
-    OCHK(c, hipEventCreateWithFlags(&ob->done, hipEventDisableTiming));
+    if (own_side && !work_stream(c->device, &ob->side)) return fail(c, LISLAM_ERR_DEVICE, "ORB stream");
+    LISLAM_HIPCHK(c, hipEventCreateWithFlags(&ob->done, hipEventDisableTiming));
     // the engines' tables and mask pyramids are uploaded / built on the side stream, where the
     // front end that reads them runs
     struct StreamSwap {
@@ -2401,28 +2379,28 @@ int orb_batch_get(lislam_batch* b, int nfeatures, const uint8_t* mask, OrbBatch*
       ~StreamSwap() { c->stream = keep; }
     } swap{c, c->stream};
     c->stream = ob->st(c);
-    ORC(engine_init(ob->e1, c, b->H, b->W, b->max_scans, nfeatures, mask));
-    ORC(engine_init(ob->e2, c, b->H, b->W, b->max_scans, 2 * nfeatures, mask));
-    ORC(ob->pb.init(c, b->max_scans, std::max(ob->e1->g.cap, ob->e2->g.cap), false));
+    LISLAM_RC(engine_init(ob->e1, c, b->H, b->W, b->max_scans, nfeatures, mask));
+    LISLAM_RC(engine_init(ob->e2, c, b->H, b->W, b->max_scans, 2 * nfeatures, mask));
+    LISLAM_RC(ob->pb.init(c, b->max_scans, std::max(ob->e1->g.cap, ob->e2->g.cap), false));
     void* q = nullptr;
-    OCHK(c, hipMalloc(&q, (size_t)b->max_scans * 7 * 8));
+    LISLAM_HIPCHK(c, hipMalloc(&q, (size_t)b->max_scans * 7 * 8));
     ob->allocs.push_back(q);
     ob->outT = static_cast<double*>(q);
-    OCHK(c, hipMalloc(&q, (size_t)b->max_scans * 8 * 4));
+    LISLAM_HIPCHK(c, hipMalloc(&q, (size_t)b->max_scans * 8 * 4));
     ob->allocs.push_back(q);
     ob->outS = static_cast<int*>(q);
     const size_t S = (size_t)b->max_scans;
     CascadeArgs& cs = ob->cs;
-    OCHK(c, hipMalloc(&q, S * 3 + 64));
+    LISLAM_HIPCHK(c, hipMalloc(&q, S * 3 + 64));
     ob->allocs.push_back(q);
     cs.pset = static_cast<int8_t*>(q); cs.cur2 = cs.pset + S; cs.have2 = cs.pset + 2 * S;
-    OCHK(c, hipMalloc(&q, (S * 8 + 8) * 4));
+    LISLAM_HIPCHK(c, hipMalloc(&q, (S * 8 + 8) * 4));
     ob->allocs.push_back(q);
     int* qi = static_cast<int*>(q);
     cs.e2list = qi; cs.plist = qi + S; cs.redet = qi + 7 * S; cs.e2cnt = qi + 8 * S; cs.pcnt = qi + 8 * S + 2;
     cs.status = qi + 8 * S + 4;
-    OCHK(c, hipHostMalloc((void**)&ob->h_status, 2 * sizeof(int), hipHostMallocDefault));
-    OCHK(c, hipEventCreateWithFlags(&ob->settled, hipEventDisableTiming));
+    LISLAM_HIPCHK(c, hipHostMalloc((void**)&ob->h_status, 2 * sizeof(int), hipHostMallocDefault));
+    LISLAM_HIPCHK(c, hipEventCreateWithFlags(&ob->settled, hipEventDisableTiming));
   }
   *out = ob;
   return LISLAM_OK;
@@ -2440,14 +2418,14 @@ int batch_intensity_odometry(lislam_batch* b, OrbBatch* ob, int n_scans) {
   hipStream_t st = c->stream;
   const uint8_t* img = b->fa.img_int;
   const float4* trk = reinterpret_cast<const float4*>(b->fa.track);
-  ORC(engine_detect_slots(ob->e1, img, trk, 0, n_scans));
+  LISLAM_RC(engine_detect_slots(ob->e1, img, trk, 0, n_scans));
   const int np = n_scans - 1;
   std::vector<int> qs(std::max(np, 1)), ts(std::max(np, 1));
   for (int k = 1; k < n_scans; k++) { qs[k - 1] = k; ts[k - 1] = k - 1; }
-  ORC(run_pairs(c, ob->e1, ob->e1, qs.data(), ts.data(), np, 0.3, ob->pb, 0, true));
+  LISLAM_RC(run_pairs(c, ob->e1, ob->e1, qs.data(), ts.data(), np, 0.3, ob->pb, 0, true));
   std::vector<int> hs((size_t)std::max(np, 1) * 8);
-  if (np > 0) OCHK(c, hipMemcpyAsync(hs.data(), ob->pb.stats, (size_t)np * 8 * 4, hipMemcpyDeviceToHost, st));
-  OCHK(c, hipStreamSynchronize(st));
+  if (np > 0) LISLAM_HIPCHK(c, hipMemcpyAsync(hs.data(), ob->pb.stats, (size_t)np * 8 * 4, hipMemcpyDeviceToHost, st));
+  LISLAM_HIPCHK(c, hipStreamSynchronize(st));
   // The sequential rule of detectfeatures: pair k re-detects both frames (2 * nfeatures, 20 %)
   // when its first attempt fails, and frame k then keeps the 2n set, against which pair k+1's
   // first attempt is made.  Resolved as a fixed point in batched rounds: cur2[k] follows from the
@@ -2463,7 +2441,7 @@ int batch_intensity_odometry(lislam_batch* b, OrbBatch* ob, int n_scans) {
       if (!have2[sc]) { have2[sc] = 1; todo.push_back(sc); }
     std::sort(todo.begin(), todo.end());
     todo.erase(std::unique(todo.begin(), todo.end()), todo.end());
-    if (!todo.empty()) ORC(engine_detect_slots(ob->e2, img, trk, 0, (int)todo.size(), todo.data()));
+    if (!todo.empty()) LISLAM_RC(engine_detect_slots(ob->e2, img, trk, 0, (int)todo.size(), todo.data()));
     return LISLAM_OK;
   };
   for (int round = 0; round < n_scans; round++) {
@@ -2474,16 +2452,16 @@ int batch_intensity_odometry(lislam_batch* b, OrbBatch* ob, int n_scans) {
     if (dirty[0].empty() && dirty[1].empty()) break;
     std::vector<int> need;
     for (int k : dirty[1]) need.push_back(k - 1);
-    ORC(detect2(need));
+    LISLAM_RC(detect2(need));
     for (int g2 = 0; g2 < 2; g2++) {
       const std::vector<int>& d = dirty[g2];
       if (d.empty()) continue;
       std::vector<int> q, t, sl;
       for (int k : d) { q.push_back(k); t.push_back(k - 1); sl.push_back(k - 1); pset[k] = g2; }
-      ORC(run_pairs(c, ob->e1, g2 ? ob->e2 : ob->e1, q.data(), t.data(), (int)d.size(), 0.3, ob->pb, 0, true, sl.data()));
+      LISLAM_RC(run_pairs(c, ob->e1, g2 ? ob->e2 : ob->e1, q.data(), t.data(), (int)d.size(), 0.3, ob->pb, 0, true, sl.data()));
     }
-    OCHK(c, hipMemcpyAsync(hs.data(), ob->pb.stats, (size_t)np * 8 * 4, hipMemcpyDeviceToHost, st));
-    OCHK(c, hipStreamSynchronize(st));
+    LISLAM_HIPCHK(c, hipMemcpyAsync(hs.data(), ob->pb.stats, (size_t)np * 8 * 4, hipMemcpyDeviceToHost, st));
+    LISLAM_HIPCHK(c, hipStreamSynchronize(st));
     for (int g2 = 0; g2 < 2; g2++)
       for (int k : dirty[g2]) ok1[k] = hs[(size_t)(k - 1) * 8] == 1;
   }
@@ -2493,15 +2471,15 @@ int batch_intensity_odometry(lislam_batch* b, OrbBatch* ob, int n_scans) {
   if (!redet.empty()) {
     std::vector<int> need, q, t, sl;
     for (int k : redet) { need.push_back(k - 1); need.push_back(k); q.push_back(k); t.push_back(k - 1); sl.push_back(k - 1); }
-    ORC(detect2(need));
-    ORC(run_pairs(c, ob->e2, ob->e2, q.data(), t.data(), (int)redet.size(), 0.2, ob->pb, 0, true, sl.data()));
+    LISLAM_RC(detect2(need));
+    LISLAM_RC(run_pairs(c, ob->e2, ob->e2, q.data(), t.data(), (int)redet.size(), 0.2, ob->pb, 0, true, sl.data()));
   }
   // outputs: scan 0 = first frame; scan k = pair (k-1, k), whose final attempt sits in slot k-1
-  OCHK(c, hipMemcpyAsync(ob->pb.redet, flag.data(), (size_t)std::max(np, 1) * 4, hipMemcpyHostToDevice, st));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(ob->pb.redet, flag.data(), (size_t)std::max(np, 1) * 4, hipMemcpyHostToDevice, st));
   const OutArgs oa{ob->outS, ob->outT, ob->pb.stats, ob->pb.T, ob->pb.redet, ob->e1->nkp, n_scans};
   hipLaunchKernelGGL(k_orb_out, dim3(cdiv(n_scans, 256)), dim3(256), 0, st, oa);
-  OCHK(c, hipGetLastError());
-  OCHK(c, hipStreamSynchronize(st));
+  LISLAM_HIPCHK(c, hipGetLastError());
+  LISLAM_HIPCHK(c, hipStreamSynchronize(st));
   return LISLAM_OK;
 }
 
@@ -2525,7 +2503,7 @@ int batch_intensity_odometry_dev(lislam_batch* b, OrbBatch* ob, int n_scans) {
   hipStream_t st = c->stream;
   const uint8_t* img = b->fa.img_int;
   const float4* trk = reinterpret_cast<const float4*>(b->fa.track);
-  ORC(engine_detect_slots(ob->e1, img, trk, 0, n_scans));
+  LISLAM_RC(engine_detect_slots(ob->e1, img, trk, 0, n_scans));
   const int np = n_scans - 1;
   std::vector<int> qs(np), ts(np);
   for (int k = 1; k < n_scans; k++) { qs[k - 1] = k; ts[k - 1] = k - 1; }
@@ -2538,22 +2516,22 @@ int batch_intensity_odometry_dev(lislam_batch* b, OrbBatch* ob, int n_scans) {
   tl.kind = 1;
   tl.mode = 0;
   tl.cs = cs;
-  ORC(run_pairs(c, ob->e1, ob->e1, qs.data(), ts.data(), np, 0.3, ob->pb, 0, true, nullptr, nullptr, nullptr, &tl));
+  LISLAM_RC(run_pairs(c, ob->e1, ob->e1, qs.data(), ts.data(), np, 0.3, ob->pb, 0, true, nullptr, nullptr, nullptr, &tl));
   const int rounds = cascade_rounds();
   for (int r = 0; r < rounds; r++) {
-    ORC(engine_select_from(ob->e2, ob->e1, img, trk, cs.e2list, cs.e2cnt, n_scans));
+    LISLAM_RC(engine_select_from(ob->e2, ob->e1, img, trk, cs.e2list, cs.e2cnt, n_scans));
     tl.mode = r + 1 < rounds ? 1 : 2;
     for (int g2 = r == 0 ? 1 : 0; g2 < 2; g2++)
-      ORC(run_pairs(c, ob->e1, g2 ? ob->e2 : ob->e1, nullptr, nullptr, n_scans, 0.3, ob->pb, 0, true, nullptr,
-                    cs.plist + (size_t)g2 * 3 * n_scans, cs.pcnt + g2, g2 == 1 ? &tl : nullptr));
+      LISLAM_RC(run_pairs(c, ob->e1, g2 ? ob->e2 : ob->e1, nullptr, nullptr, n_scans, 0.3, ob->pb, 0, true, nullptr,
+                          cs.plist + (size_t)g2 * 3 * n_scans, cs.pcnt + g2, g2 == 1 ? &tl : nullptr));
   }
-  ORC(engine_select_from(ob->e2, ob->e1, img, trk, cs.e2list, cs.e2cnt, n_scans));
+  LISLAM_RC(engine_select_from(ob->e2, ob->e1, img, trk, cs.e2list, cs.e2cnt, n_scans));
   tl.kind = 2;
   tl.out = OutArgs{ob->outS, ob->outT, ob->pb.stats, ob->pb.T, cs.redet, ob->e1->nkp, n_scans};
-  ORC(run_pairs(c, ob->e2, ob->e2, nullptr, nullptr, n_scans, 0.2, ob->pb, 0, true, nullptr, cs.plist, cs.pcnt, &tl));
-  OCHK(c, hipGetLastError());
-  OCHK(c, hipMemcpyAsync(ob->h_status, cs.status, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
-  OCHK(c, hipEventRecord(ob->settled, st));
+  LISLAM_RC(run_pairs(c, ob->e2, ob->e2, nullptr, nullptr, n_scans, 0.2, ob->pb, 0, true, nullptr, cs.plist, cs.pcnt, &tl));
+  LISLAM_HIPCHK(c, hipGetLastError());
+  LISLAM_HIPCHK(c, hipMemcpyAsync(ob->h_status, cs.status, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
+  LISLAM_HIPCHK(c, hipEventRecord(ob->settled, st));
   ob->pending = true;
   ob->pending_n = n_scans;
   return LISLAM_OK;
@@ -2569,14 +2547,14 @@ int orb_settle(lislam_batch* b) {
   OrbBatch* ob = static_cast<OrbBatch*>(b->orb);
   if (!ob || !ob->pending) return LISLAM_OK;
   lislam_ctx* c = b->ctx;
-  OCHK(c, hipEventSynchronize(ob->settled));
+  LISLAM_HIPCHK(c, hipEventSynchronize(ob->settled));
   ob->pending = false;
   ob->info[0] = ob->h_status[0];
   ob->info[1] = ob->h_status[1];
   if (ob->h_status[0] == 1) return LISLAM_OK;
   const hipStream_t main_stream = c->stream;
   const hipStream_t side = ob->st(c);
-  if (side != main_stream) OCHK(c, hipStreamWaitEvent(side, b->ev_images, 0));
+  if (side != main_stream) LISLAM_HIPCHK(c, hipStreamWaitEvent(side, b->ev_images, 0));
   c->stream = side;
   const int rc = batch_intensity_odometry(b, ob, ob->pending_n);
   c->stream = main_stream;
@@ -2594,14 +2572,14 @@ int lislam_batch_intensity_odometry(lislam_batch* b, int32_t n_scans, int32_t nf
   if (!b || n_scans < 1 || n_scans > b->max_scans || nfeatures < 1 || nfeatures > 16384) return LISLAM_ERR_ARG;
   lislam_ctx* c = b->ctx;
   if (!b->fa.img_int || !b->fa.track)
-    return ofail(c, LISLAM_ERR_STATE, "lislam_batch_intensity_odometry needs want_images (the a1 images)");
-  if (b->extracted < n_scans) return ofail(c, LISLAM_ERR_STATE, "extract %d scans before intensity odometry", n_scans);
+    return fail(c, LISLAM_ERR_STATE, "lislam_batch_intensity_odometry needs want_images (the a1 images)");
+  if (b->extracted < n_scans) return fail(c, LISLAM_ERR_STATE, "extract %d scans before intensity odometry", n_scans);
   hipSetDevice(c->device);
   OrbBatch* ob = nullptr;
-  ORC(orb_batch_get(b, nfeatures, mask, &ob));
+  LISLAM_RC(orb_batch_get(b, nfeatures, mask, &ob));
   const hipStream_t main_stream = c->stream;
   const hipStream_t side = ob->st(c);
-  if (side != main_stream) OCHK(c, hipStreamWaitEvent(side, b->ev_images, 0));
+  if (side != main_stream) LISLAM_HIPCHK(c, hipStreamWaitEvent(side, b->ev_images, 0));
   c->stream = side;
   ob->pending = false;  // a newer batch replaces results nobody read
   ob->info[0] = -1;
@@ -2610,8 +2588,8 @@ int lislam_batch_intensity_odometry(lislam_batch* b, int32_t n_scans, int32_t nf
                                                                                : batch_intensity_odometry_dev(b, ob, n_scans);
   c->stream = main_stream;
   if (side != main_stream) {
-    OCHK(c, hipEventRecord(ob->done, side));
-    OCHK(c, hipStreamWaitEvent(main_stream, ob->done, 0));
+    LISLAM_HIPCHK(c, hipEventRecord(ob->done, side));
+    LISLAM_HIPCHK(c, hipStreamWaitEvent(main_stream, ob->done, 0));
   }
   ob->ran_n = rc == LISLAM_OK ? n_scans : 0;
   return rc;
@@ -2666,30 +2644,30 @@ int lislam_intensity_tracker_step(lislam_intensity_tracker* t, const uint8_t* im
   hipStream_t st = c->stream;
   const size_t N = (size_t)t->H * t->W;
   const int cs = t->cur, ps = 1 - t->cur;
-  OCHK(c, hipMemcpyAsync(t->img + cs * N, image, N, hipMemcpyDefault, st));
-  OCHK(c, hipMemcpyAsync(t->trk + cs * N, cloud_track, N * 16, hipMemcpyDefault, st));
-  ORC(engine_detect_slots(&t->e1, t->img, t->trk, cs, 1));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(t->img + cs * N, image, N, hipMemcpyDefault, st));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(t->trk + cs * N, cloud_track, N * 16, hipMemcpyDefault, st));
+  LISLAM_RC(engine_detect_slots(&t->e1, t->img, t->trk, cs, 1));
   int h8[8] = {-1, 0, 0, 0, 0, 0, 0, 0};
   double T[7] = {0, 0, 0, 1, 0, 0, 0};
   bool cur2 = false;
   if (!t->have_prev) {
-    OCHK(c, hipMemcpyAsync(&h8[2], t->e1.nkp + cs, 4, hipMemcpyDeviceToHost, st));
-    OCHK(c, hipStreamSynchronize(st));
+    LISLAM_HIPCHK(c, hipMemcpyAsync(&h8[2], t->e1.nkp + cs, 4, hipMemcpyDeviceToHost, st));
+    LISLAM_HIPCHK(c, hipStreamSynchronize(st));
   } else {
-    ORC(run_pairs(c, &t->e1, t->prev2 ? &t->e2 : &t->e1, &cs, &ps, 1, 0.3, t->pb, 0, true));
-    OCHK(c, hipMemcpyAsync(h8, t->pb.stats, 32, hipMemcpyDeviceToHost, st));
-    OCHK(c, hipStreamSynchronize(st));
+    LISLAM_RC(run_pairs(c, &t->e1, t->prev2 ? &t->e2 : &t->e1, &cs, &ps, 1, 0.3, t->pb, 0, true));
+    LISLAM_HIPCHK(c, hipMemcpyAsync(h8, t->pb.stats, 32, hipMemcpyDeviceToHost, st));
+    LISLAM_HIPCHK(c, hipStreamSynchronize(st));
     if (h8[0] != 1) {  // re-detect both frames with 2 * nfeatures (intensity_feature_tracker.cpp:652-687)
-      ORC(engine_detect_slots(&t->e2, t->img, t->trk, cs, 1));
-      if (!t->prev2) ORC(engine_detect_slots(&t->e2, t->img, t->trk, ps, 1));
-      ORC(run_pairs(c, &t->e2, &t->e2, &cs, &ps, 1, 0.2, t->pb, 0, true));
-      OCHK(c, hipMemcpyAsync(h8, t->pb.stats, 32, hipMemcpyDeviceToHost, st));
-      OCHK(c, hipStreamSynchronize(st));
+      LISLAM_RC(engine_detect_slots(&t->e2, t->img, t->trk, cs, 1));
+      if (!t->prev2) LISLAM_RC(engine_detect_slots(&t->e2, t->img, t->trk, ps, 1));
+      LISLAM_RC(run_pairs(c, &t->e2, &t->e2, &cs, &ps, 1, 0.2, t->pb, 0, true));
+      LISLAM_HIPCHK(c, hipMemcpyAsync(h8, t->pb.stats, 32, hipMemcpyDeviceToHost, st));
+      LISLAM_HIPCHK(c, hipStreamSynchronize(st));
       h8[1] = 1;
       cur2 = true;
     }
-    OCHK(c, hipMemcpyAsync(T, t->pb.T, 56, hipMemcpyDeviceToHost, st));
-    OCHK(c, hipStreamSynchronize(st));
+    LISLAM_HIPCHK(c, hipMemcpyAsync(T, t->pb.T, 56, hipMemcpyDeviceToHost, st));
+    LISLAM_HIPCHK(c, hipStreamSynchronize(st));
   }
   t->have_prev = true;
   t->prev2 = cur2;
@@ -2708,25 +2686,25 @@ static int orb_detect_impl(lislam_ctx* c, const uint8_t* image, const float* clo
   hipStream_t st = c->stream;
   OrbEngine e;
   e.map_filter = map_filter;
-  ORC(engine_init(&e, c, H, W, 1, nfeatures, mask));
+  LISLAM_RC(engine_init(&e, c, H, W, 1, nfeatures, mask));
   uint8_t* dimg = nullptr;
   float4* dtrk = nullptr;
-  ORC(e.alloc(&dimg, (size_t)H * W));
-  ORC(e.alloc(&dtrk, (size_t)H * W));
-  OCHK(c, hipMemcpyAsync(dimg, image, (size_t)H * W, hipMemcpyDefault, st));
-  OCHK(c, hipMemcpyAsync(dtrk, cloud_track, (size_t)H * W * 16, hipMemcpyDefault, st));
-  ORC(engine_detect_slots(&e, dimg, dtrk, 0, 1));
+  LISLAM_RC(e.alloc(&dimg, (size_t)H * W));
+  LISLAM_RC(e.alloc(&dtrk, (size_t)H * W));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(dimg, image, (size_t)H * W, hipMemcpyDefault, st));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(dtrk, cloud_track, (size_t)H * W * 16, hipMemcpyDefault, st));
+  LISLAM_RC(engine_detect_slots(&e, dimg, dtrk, 0, 1));
   int cnt = 0, ovf = 0;
-  OCHK(c, hipMemcpyAsync(&cnt, e.nkp, 4, hipMemcpyDeviceToHost, st));
-  OCHK(c, hipMemcpyAsync(&ovf, e.overflow, 4, hipMemcpyDeviceToHost, st));
-  OCHK(c, hipStreamSynchronize(st));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(&cnt, e.nkp, 4, hipMemcpyDeviceToHost, st));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(&ovf, e.overflow, 4, hipMemcpyDeviceToHost, st));
+  LISLAM_HIPCHK(c, hipStreamSynchronize(st));
   *n = cnt;
-  if (ovf) return ofail(c, LISLAM_ERR_CAPACITY, "ORB level keypoint capacity exceeded");
-  if (cnt > cap) return ofail(c, LISLAM_ERR_CAPACITY, "lislam_orb_detect: %d keypoints > cap %d", cnt, cap);
-  if (kp) OCHK(c, hipMemcpyAsync(kp, e.kp, (size_t)cnt * 24, hipMemcpyDefault, st));
-  if (desc) OCHK(c, hipMemcpyAsync(desc, e.desc, (size_t)cnt * 32, hipMemcpyDefault, st));
-  if (p3d) OCHK(c, hipMemcpyAsync(p3d, e.p3d, (size_t)cnt * 16, hipMemcpyDefault, st));
-  OCHK(c, hipStreamSynchronize(st));
+  if (ovf) return fail(c, LISLAM_ERR_CAPACITY, "ORB level keypoint capacity exceeded");
+  if (cnt > cap) return fail(c, LISLAM_ERR_CAPACITY, "lislam_orb_detect: %d keypoints > cap %d", cnt, cap);
+  if (kp) LISLAM_HIPCHK(c, hipMemcpyAsync(kp, e.kp, (size_t)cnt * 24, hipMemcpyDefault, st));
+  if (desc) LISLAM_HIPCHK(c, hipMemcpyAsync(desc, e.desc, (size_t)cnt * 32, hipMemcpyDefault, st));
+  if (p3d) LISLAM_HIPCHK(c, hipMemcpyAsync(p3d, e.p3d, (size_t)cnt * 16, hipMemcpyDefault, st));
+  LISLAM_HIPCHK(c, hipStreamSynchronize(st));
   return LISLAM_OK;
 }
 
@@ -2751,24 +2729,24 @@ int lislam_orb_match(lislam_ctx* c, const uint8_t* qdesc, int32_t nq, const uint
   e.ctx = c;
   const int cap = std::max(std::max(nq, nt), 1);
   e.g.cap = cap;
-  ORC(e.alloc(&e.desc, (size_t)2 * cap * 32));
-  ORC(e.alloc(&e.p3d, (size_t)2 * cap));
-  ORC(e.alloc(&e.nkp, 2));
+  LISLAM_RC(e.alloc(&e.desc, (size_t)2 * cap * 32));
+  LISLAM_RC(e.alloc(&e.p3d, (size_t)2 * cap));
+  LISLAM_RC(e.alloc(&e.nkp, 2));
   const int cnts[2] = {nq, nt};
-  OCHK(c, hipMemcpyAsync(e.nkp, cnts, 8, hipMemcpyHostToDevice, st));
-  OCHK(c, hipMemsetAsync(e.p3d, 0, (size_t)2 * cap * 16, st));
-  if (nq) OCHK(c, hipMemcpyAsync(e.desc, qdesc, (size_t)nq * 32, hipMemcpyDefault, st));
-  if (nt) OCHK(c, hipMemcpyAsync(e.desc + (size_t)cap * 32, tdesc, (size_t)nt * 32, hipMemcpyDefault, st));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(e.nkp, cnts, 8, hipMemcpyHostToDevice, st));
+  LISLAM_HIPCHK(c, hipMemsetAsync(e.p3d, 0, (size_t)2 * cap * 16, st));
+  if (nq) LISLAM_HIPCHK(c, hipMemcpyAsync(e.desc, qdesc, (size_t)nq * 32, hipMemcpyDefault, st));
+  if (nt) LISLAM_HIPCHK(c, hipMemcpyAsync(e.desc + (size_t)cap * 32, tdesc, (size_t)nt * 32, hipMemcpyDefault, st));
   PairBufs pb;
-  ORC(pb.init(c, 1, cap, true));
+  LISLAM_RC(pb.init(c, 1, cap, true));
   const int q = 0, t = 1;
-  ORC(run_pairs(c, &e, &e, &q, &t, 1, 0.3, pb, 0, false));
+  LISLAM_RC(run_pairs(c, &e, &e, &q, &t, 1, 0.3, pb, 0, false));
   int h8[8];
-  OCHK(c, hipMemcpyAsync(h8, pb.stats, 32, hipMemcpyDeviceToHost, st));
-  OCHK(c, hipStreamSynchronize(st));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(h8, pb.stats, 32, hipMemcpyDeviceToHost, st));
+  LISLAM_HIPCHK(c, hipStreamSynchronize(st));
   *n_matches = h8[3];
-  if (matches && h8[3]) OCHK(c, hipMemcpyAsync(matches, pb.mout, (size_t)h8[3] * 12, hipMemcpyDefault, st));
-  OCHK(c, hipStreamSynchronize(st));
+  if (matches && h8[3]) LISLAM_HIPCHK(c, hipMemcpyAsync(matches, pb.mout, (size_t)h8[3] * 12, hipMemcpyDefault, st));
+  LISLAM_HIPCHK(c, hipStreamSynchronize(st));
   return LISLAM_OK;
 }
 
@@ -2779,7 +2757,7 @@ extern "C" int lislam_batch_orb_cascade_info(lislam_batch* b, int32_t* info) {
   if (!b || !info) return LISLAM_ERR_ARG;
   OrbBatch* ob = static_cast<OrbBatch*>(b->orb);
   if (!ob) return LISLAM_ERR_STATE;
-  ORC(orb_settle(b));
+  LISLAM_RC(orb_settle(b));
   info[0] = ob->info[0];
   info[1] = ob->info[1];
   return LISLAM_OK;
@@ -2788,7 +2766,7 @@ extern "C" int lislam_batch_orb_cascade_info(lislam_batch* b, int32_t* info) {
 int lislam_orb_batch_output(lislam_batch* b, int what, int scan, const void** src, int* cnt, size_t* esz) {
   OrbBatch* ob = static_cast<OrbBatch*>(b->orb);
   if (!ob) return LISLAM_ERR_STATE;
-  ORC(orb_settle(b));
+  LISLAM_RC(orb_settle(b));
   const Geom& g = ob->e1->g;
   switch (what) {
     case LISLAM_OUT_ORB_T: *src = ob->outT + (size_t)scan * 7; *cnt = 7; *esz = 8; return LISLAM_OK;
@@ -2815,7 +2793,7 @@ int lislam_orb_batch_descriptors(lislam_batch* b, const uint8_t** desc, const in
                                  int* n_scans) {
   OrbBatch* ob = static_cast<OrbBatch*>(b->orb);
   if (!ob || ob->ran_n == 0) return LISLAM_ERR_STATE;
-  ORC(orb_settle(b));
+  LISLAM_RC(orb_settle(b));
   *desc = ob->e1->desc;
   *counts = ob->e1->nkp;
   *cap = ob->e1->g.cap;

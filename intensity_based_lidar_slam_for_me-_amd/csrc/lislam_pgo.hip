@@ -37,6 +37,7 @@
 #include "lislam_batch.hpp"
 #include "lislam_ctx.hpp"
 #include "lislam_device.hpp"
+#include "lislam_host.hpp"
 
 namespace lislam {
 namespace pgo {
@@ -724,6 +725,7 @@ __global__ __launch_bounds__(kThreads) void k_pgo_pose6d(int n, const double* __
 }  // namespace lislam
 
 using namespace lislam::pgo;
+using namespace lislam;
 
 struct lislam_pgo {
   lislam_ctx* ctx = nullptr;
@@ -742,8 +744,7 @@ struct lislam_pgo {
   double* added[2] = {nullptr, nullptr};
   int added_cur = 0;
   // grow-only staging of lislam_pgo_add_keyframes: [pose7 n_poses x 7][index n]
-  void* kstage = nullptr;
-  size_t kstage_bytes = 0;
+  DBuf kstage;
   int *adj_off = nullptr, *adj = nullptr;
   Blocks b{};
   double *Hd = nullptr, *U = nullptr, *g = nullptr, *Sinv = nullptr, *L = nullptr;
@@ -759,24 +760,6 @@ namespace {
 
 const double kOdometryVariances[6] = {1e-6, 1e-6, 1e-6, 1e-8, 1e-8, 1e-6};  // odometryNoise_ (:41-44)
 
-int gfail(lislam_ctx* c, int code, const char* fmt, ...) {
-  if (c) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    c->err = buf;
-  }
-  return code;
-}
-
-#define GCHK(ctx, x)                                                                                  \
-  do {                                                                                                \
-    hipError_t e_ = (x);                                                                              \
-    if (e_ != hipSuccess) return gfail(ctx, LISLAM_ERR_DEVICE, "%s: %s", #x, hipGetErrorString(e_)); \
-  } while (0)
-
 template <typename T>
 bool dalloc(lislam_pgo* p, T** out, size_t count) {
   void* q = nullptr;
@@ -789,7 +772,6 @@ bool dalloc(lislam_pgo* p, T** out, size_t count) {
 void free_pgo(lislam_pgo* p) {
   for (void* q : p->allocs) (void)hipFree(q);
   if (p->h_res) (void)hipHostFree(p->h_res);
-  if (p->kstage) (void)hipFree(p->kstage);
   delete p;
 }
 
@@ -819,9 +801,9 @@ int sync_adjacency(lislam_pgo* p) {
     inc[fill[p->h_to[k]]++] = 2 * k + 1;
   }
   if (p->prior_node >= 0) inc[fill[p->prior_node]++] = 2 * p->e + 1;
-  GCHK(c, hipMemcpyAsync(p->adj_off, off.data(), off.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  GCHK(c, hipMemcpyAsync(p->adj, inc.data(), inc.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  GCHK(c, hipStreamSynchronize(c->stream));  // the vectors leave scope
+  LISLAM_HIPCHK(c, hipMemcpyAsync(p->adj_off, off.data(), off.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(p->adj, inc.data(), inc.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  LISLAM_HIPCHK(c, hipStreamSynchronize(c->stream));  // the vectors leave scope
   p->adj_dirty = false;
   return LISLAM_OK;
 }
@@ -832,7 +814,7 @@ void launch_linearize(lislam_pgo* p, const double* x) {
 }
 
 int ready(lislam_pgo* p, const char* who) {
-  if (p->n > 0 && p->prior_node < 0) return gfail(p->ctx, LISLAM_ERR_STATE, "%s: set a prior first (lislam_pgo_set_prior)", who);
+  if (p->n > 0 && p->prior_node < 0) return fail(p->ctx, LISLAM_ERR_STATE, "%s: set a prior first (lislam_pgo_set_prior)", who);
   return LISLAM_OK;
 }
 
@@ -846,10 +828,10 @@ int lislam_pgo_create(lislam_ctx* c, const lislam_pgo_config* cfg, int32_t node_
   lislam_pgo_config d = {50, 0, 1e-4, 1e-10, 1e-12};
   if (cfg) d = *cfg;
   if (node_capacity < 1 || edge_capacity < 0 || node_capacity > (1 << 24) || edge_capacity > (1 << 24))
-    return gfail(c, LISLAM_ERR_ARG, "lislam_pgo_create: node_capacity 1..2^24, edge_capacity 0..2^24");
+    return fail(c, LISLAM_ERR_ARG, "lislam_pgo_create: node_capacity 1..2^24, edge_capacity 0..2^24");
   if (d.max_iterations < 0 || d.cg_max_iterations < 0 || !(d.lambda_init > 0) || !std::isfinite(d.lambda_init) ||
       !(d.rel_cost_tol >= 0) || !(d.cg_rel_tol >= 0))
-    return gfail(c, LISLAM_ERR_ARG, "lislam_pgo_create: invalid configuration");
+    return fail(c, LISLAM_ERR_ARG, "lislam_pgo_create: invalid configuration");
   hipSetDevice(c->device);
   lislam_pgo* p = new lislam_pgo();
   p->ctx = c;
@@ -870,7 +852,7 @@ int lislam_pgo_create(lislam_ctx* c, const lislam_pgo_config* cfg, int32_t node_
   if (!ok) {
     (void)hipGetLastError();
     free_pgo(p);
-    return gfail(c, LISLAM_ERR_DEVICE, "lislam_pgo_create: device allocation failed");
+    return fail(c, LISLAM_ERR_DEVICE, "lislam_pgo_create: device allocation failed");
   }
   p->h_from.reserve(E);
   p->h_to.reserve(E);
@@ -898,14 +880,14 @@ int lislam_pgo_add_nodes(lislam_pgo* p, const double* pose7, int32_t n) {
   lislam_ctx* c = p->ctx;
   if (n == 0) return LISLAM_OK;
   if ((int64_t)p->n + n > p->ncap)
-    return gfail(c, LISLAM_ERR_CAPACITY, "lislam_pgo_add_nodes: %d + %d nodes exceed the capacity %d", p->n, n, p->ncap);
+    return fail(c, LISLAM_ERR_CAPACITY, "lislam_pgo_add_nodes: %d + %d nodes exceed the capacity %d", p->n, n, p->ncap);
   for (int k = 0; k < n; k++)
-    if (!finite_pose(pose7 + (size_t)k * 7)) return gfail(c, LISLAM_ERR_ARG, "lislam_pgo_add_nodes: pose %d is not finite", k);
+    if (!finite_pose(pose7 + (size_t)k * 7)) return fail(c, LISLAM_ERR_ARG, "lislam_pgo_add_nodes: pose %d is not finite", k);
   hipSetDevice(c->device);
-  GCHK(c, hipMemcpyAsync(p->x[p->cur] + (size_t)p->n * 7, pose7, (size_t)n * 7 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  GCHK(c, hipMemcpyAsync(p->added[p->added_cur], pose7 + (size_t)(n - 1) * 7, 7 * sizeof(double), hipMemcpyHostToDevice,
-                         c->stream));
-  GCHK(c, hipStreamSynchronize(c->stream));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(p->x[p->cur] + (size_t)p->n * 7, pose7, (size_t)n * 7 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(p->added[p->added_cur], pose7 + (size_t)(n - 1) * 7, 7 * sizeof(double), hipMemcpyHostToDevice,
+                                  c->stream));
+  LISLAM_HIPCHK(c, hipStreamSynchronize(c->stream));
   p->n += n;
   p->adj_dirty = true;
   return LISLAM_OK;
@@ -914,14 +896,14 @@ int lislam_pgo_add_nodes(lislam_pgo* p, const double* pose7, int32_t n) {
 int lislam_pgo_set_prior(lislam_pgo* p, int32_t node, const double* pose7, const double* var6) {
   if (!p || !pose7 || !var6) return LISLAM_ERR_ARG;
   lislam_ctx* c = p->ctx;
-  if (node < 0 || node >= p->n) return gfail(c, LISLAM_ERR_ARG, "lislam_pgo_set_prior: node %d out of range (size %d)", node, p->n);
-  if (!positive(var6, 6) || !finite_pose(pose7)) return gfail(c, LISLAM_ERR_ARG, "lislam_pgo_set_prior: variances must be positive, the pose finite");
+  if (node < 0 || node >= p->n) return fail(c, LISLAM_ERR_ARG, "lislam_pgo_set_prior: node %d out of range (size %d)", node, p->n);
+  if (!positive(var6, 6) || !finite_pose(pose7)) return fail(c, LISLAM_ERR_ARG, "lislam_pgo_set_prior: variances must be positive, the pose finite");
   double h[13];
   for (int k = 0; k < 7; k++) h[k] = pose7[k];
   for (int k = 0; k < 6; k++) h[7 + k] = std::sqrt(var6[k]);
   hipSetDevice(c->device);
-  GCHK(c, hipMemcpyAsync(p->prior, h, sizeof(h), hipMemcpyHostToDevice, c->stream));
-  GCHK(c, hipStreamSynchronize(c->stream));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(p->prior, h, sizeof(h), hipMemcpyHostToDevice, c->stream));
+  LISLAM_HIPCHK(c, hipStreamSynchronize(c->stream));
   p->prior_node = node;
   p->adj_dirty = true;
   return LISLAM_OK;
@@ -934,12 +916,12 @@ int lislam_pgo_add_edges(lislam_pgo* p, const int32_t* from, const int32_t* to, 
   if (n == 0) return LISLAM_OK;
   for (int k = 0; k < n; k++) {
     if (from[k] < 0 || from[k] >= p->n || to[k] < 0 || to[k] >= p->n || from[k] == to[k])
-      return gfail(c, LISLAM_ERR_ARG, "lislam_pgo_add_edges: edge %d = (%d, %d) invalid (size %d)", k, from[k], to[k], p->n);
+      return fail(c, LISLAM_ERR_ARG, "lislam_pgo_add_edges: edge %d = (%d, %d) invalid (size %d)", k, from[k], to[k], p->n);
     if (!positive(var6 + (size_t)k * 6, 6) || !finite_pose(meas7 + (size_t)k * 7))
-      return gfail(c, LISLAM_ERR_ARG, "lislam_pgo_add_edges: edge %d: variances must be positive, the measurement finite", k);
+      return fail(c, LISLAM_ERR_ARG, "lislam_pgo_add_edges: edge %d: variances must be positive, the measurement finite", k);
   }
   if ((int64_t)p->e + n > p->ecap)
-    return gfail(c, LISLAM_ERR_CAPACITY, "lislam_pgo_add_edges: %d + %d edges exceed the capacity %d", p->e, n, p->ecap);
+    return fail(c, LISLAM_ERR_CAPACITY, "lislam_pgo_add_edges: %d + %d edges exceed the capacity %d", p->e, n, p->ecap);
   std::vector<double> sg((size_t)n * 6);
   std::vector<int> rb(n, 0);
   for (size_t k = 0; k < sg.size(); k++) sg[k] = std::sqrt(var6[k]);
@@ -947,12 +929,12 @@ int lislam_pgo_add_edges(lislam_pgo* p, const int32_t* from, const int32_t* to, 
     for (int k = 0; k < n; k++) rb[k] = robust[k] != 0;
   hipSetDevice(c->device);
   const size_t at = (size_t)p->e;
-  GCHK(c, hipMemcpyAsync(p->from + at, from, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-  GCHK(c, hipMemcpyAsync(p->to + at, to, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-  GCHK(c, hipMemcpyAsync(p->robust + at, rb.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-  GCHK(c, hipMemcpyAsync(p->meas + at * 7, meas7, (size_t)n * 7 * 8, hipMemcpyHostToDevice, c->stream));
-  GCHK(c, hipMemcpyAsync(p->sigma + at * 6, sg.data(), (size_t)n * 6 * 8, hipMemcpyHostToDevice, c->stream));
-  GCHK(c, hipStreamSynchronize(c->stream));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(p->from + at, from, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(p->to + at, to, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(p->robust + at, rb.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(p->meas + at * 7, meas7, (size_t)n * 7 * 8, hipMemcpyHostToDevice, c->stream));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(p->sigma + at * 6, sg.data(), (size_t)n * 6 * 8, hipMemcpyHostToDevice, c->stream));
+  LISLAM_HIPCHK(c, hipStreamSynchronize(c->stream));
   p->h_from.insert(p->h_from.end(), from, from + n);
   p->h_to.insert(p->h_to.end(), to, to + n);
   p->e += n;
@@ -963,32 +945,31 @@ int lislam_pgo_add_edges(lislam_pgo* p, const int32_t* from, const int32_t* to, 
 int lislam_pgo_add_batch(lislam_pgo* p, lislam_batch* b, int32_t first_scan, int32_t n_scans, const double* var6) {
   if (!p || !b) return LISLAM_ERR_ARG;
   lislam_ctx* c = p->ctx;
-  if (b->ctx != c) return gfail(c, LISLAM_ERR_ARG, "lislam_pgo_add_batch: the batch belongs to another context");
-  if (first_scan < 0 || n_scans < 0 || (int64_t)first_scan + n_scans > b->max_scans)
-    return gfail(c, LISLAM_ERR_ARG, "lislam_pgo_add_batch: scans [%d, %d + %d) out of range", first_scan, first_scan, n_scans);
-  if (var6 && !positive(var6, 6)) return gfail(c, LISLAM_ERR_ARG, "lislam_pgo_add_batch: variances must be positive");
+  LISLAM_RC(check_same_context(c, "lislam_pgo_add_batch", b));
+  LISLAM_RC(check_scan_range(c, "lislam_pgo_add_batch", b, first_scan, n_scans));
+  if (var6 && !positive(var6, 6)) return fail(c, LISLAM_ERR_ARG, "lislam_pgo_add_batch: variances must be positive");
   if (first_scan + n_scans > b->extracted)
-    return gfail(c, LISLAM_ERR_STATE, "lislam_pgo_add_batch: extract and run the odometry of %d scans first", first_scan + n_scans);
+    return fail(c, LISLAM_ERR_STATE, "lislam_pgo_add_batch: extract and run the odometry of %d scans first", first_scan + n_scans);
   if (n_scans == 0) return LISLAM_OK;
   // the scan before `first_scan` anchors the first new node when the graph already holds its node
   const int k0 = (p->n > 0 && first_scan > 0) ? 0 : 1;
   const int n_edges = n_scans - k0;
   if ((int64_t)p->n + n_scans > p->ncap || (int64_t)p->e + n_edges > p->ecap)
-    return gfail(c, LISLAM_ERR_CAPACITY, "lislam_pgo_add_batch: %d + %d nodes / %d + %d edges exceed the capacity %d / %d", p->n,
-                 n_scans, p->e, n_edges, p->ncap, p->ecap);
+    return fail(c, LISLAM_ERR_CAPACITY, "lislam_pgo_add_batch: %d + %d nodes / %d + %d edges exceed the capacity %d / %d", p->n,
+                n_scans, p->e, n_edges, p->ncap, p->ecap);
   int rc = lislam_batch_settle(b);
   if (rc != LISLAM_OK) return rc;
   hipSetDevice(c->device);
   double sg[6];
   for (int k = 0; k < 6; k++) sg[k] = std::sqrt(var6 ? var6[k] : kOdometryVariances[k]);
-  GCHK(c, hipMemcpyAsync(p->odom_sigma, sg, sizeof(sg), hipMemcpyHostToDevice, c->stream));
-  GCHK(c, hipStreamSynchronize(c->stream));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(p->odom_sigma, sg, sizeof(sg), hipMemcpyHostToDevice, c->stream));
+  LISLAM_HIPCHK(c, hipStreamSynchronize(c->stream));
   hipLaunchKernelGGL(k_pgo_add_batch, dim3((n_scans + kThreads - 1) / kThreads), dim3(kThreads), 0, c->stream, n_scans, k0,
                      b->oa.pose + (size_t)first_scan * 7, p->n, p->e, p->x[p->cur], p->from, p->to, p->meas, p->sigma, p->robust,
                      p->odom_sigma);
-  GCHK(c, hipGetLastError());
-  GCHK(c, hipMemcpyAsync(p->added[p->added_cur], b->oa.pose + (size_t)(first_scan + n_scans - 1) * 7, 7 * sizeof(double),
-                         hipMemcpyDeviceToDevice, c->stream));
+  LISLAM_HIPCHK(c, hipGetLastError());
+  LISLAM_HIPCHK(c, hipMemcpyAsync(p->added[p->added_cur], b->oa.pose + (size_t)(first_scan + n_scans - 1) * 7, 7 * sizeof(double),
+                                  hipMemcpyDeviceToDevice, c->stream));
   for (int k = k0; k < n_scans; k++) {
     p->h_from.push_back(p->n + k - 1);
     p->h_to.push_back(p->n + k);
@@ -1009,35 +990,26 @@ int add_keyframes(lislam_pgo* p, const char* who, const double* d_pose, const do
   const int k0 = p->n > 0 ? 0 : 1;
   const int n_edges = n - k0;
   if ((int64_t)p->n + n > p->ncap || (int64_t)p->e + n_edges > p->ecap)
-    return gfail(c, LISLAM_ERR_CAPACITY, "%s: %d + %d nodes / %d + %d edges exceed the capacity %d / %d", who, p->n, n, p->e,
-                 n_edges, p->ncap, p->ecap);
+    return fail(c, LISLAM_ERR_CAPACITY, "%s: %d + %d nodes / %d + %d edges exceed the capacity %d / %d", who, p->n, n, p->e,
+                n_edges, p->ncap, p->ecap);
   hipSetDevice(c->device);
   const size_t staged = d_pose ? 0 : (size_t)n_poses * 7 * sizeof(double);
   const size_t want = staged + (size_t)n * sizeof(int);
-  if (want > p->kstage_bytes) {
-    if (p->kstage) {
-      GCHK(c, hipStreamSynchronize(c->stream));
-      (void)hipFree(p->kstage);
-      p->kstage = nullptr;
-      p->kstage_bytes = 0;
-    }
-    GCHK(c, hipMalloc(&p->kstage, want));
-    p->kstage_bytes = want;
-  }
-  int* d_index = reinterpret_cast<int*>(static_cast<char*>(p->kstage) + staged);
+  LISLAM_HIPCHK(c, p->kstage.reserve(want, c->stream));
+  int* d_index = reinterpret_cast<int*>(p->kstage.as<char>() + staged);
   double sg[6];
   for (int k = 0; k < 6; k++) sg[k] = std::sqrt(var6 ? var6[k] : kOdometryVariances[k]);
   if (!d_pose) {
-    GCHK(c, hipMemcpyAsync(p->kstage, pose7, staged, hipMemcpyDefault, c->stream));
-    d_pose = static_cast<const double*>(p->kstage);
+    LISLAM_HIPCHK(c, hipMemcpyAsync(p->kstage.p, pose7, staged, hipMemcpyDefault, c->stream));
+    d_pose = p->kstage.as<const double>();
   }
-  GCHK(c, hipMemcpyAsync(d_index, index, (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  GCHK(c, hipMemcpyAsync(p->odom_sigma, sg, sizeof(sg), hipMemcpyHostToDevice, c->stream));
-  GCHK(c, hipStreamSynchronize(c->stream));  // sg leaves scope
+  LISLAM_HIPCHK(c, hipMemcpyAsync(d_index, index, (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(p->odom_sigma, sg, sizeof(sg), hipMemcpyHostToDevice, c->stream));
+  LISLAM_HIPCHK(c, hipStreamSynchronize(c->stream));  // sg leaves scope
   hipLaunchKernelGGL(k_pgo_add_keyframes, dim3((n + kThreads - 1) / kThreads), dim3(kThreads), 0, c->stream, n, k0, d_pose,
                      d_index, p->added[p->added_cur], p->added[p->added_cur ^ 1], p->n, p->e, p->x[p->cur], p->from, p->to,
                      p->meas, p->sigma, p->robust, p->odom_sigma);
-  GCHK(c, hipGetLastError());
+  LISLAM_HIPCHK(c, hipGetLastError());
   p->added_cur ^= 1;
   for (int k = k0; k < n; k++) {
     p->h_from.push_back(p->n + k - 1);
@@ -1049,26 +1021,14 @@ int add_keyframes(lislam_pgo* p, const char* who, const double* d_pose, const do
   return LISLAM_OK;
 }
 
-int check_index(lislam_ctx* c, const char* who, const char* name, const int32_t* index, int n, int bound) {
-  for (int k = 0; k < n; k++) {
-    if (index[k] < 0 || index[k] >= bound)
-      return gfail(c, LISLAM_ERR_ARG, "%s: %s[%d] = %d outside [0, %d)", who, name, k, index[k], bound);
-    if (k > 0 && index[k] <= index[k - 1])
-      return gfail(c, LISLAM_ERR_ARG, "%s: %s[%d] = %d after %d: the list must be strictly increasing", who, name, k, index[k],
-                   index[k - 1]);
-  }
-  return LISLAM_OK;
-}
-
 }  // namespace
 
 int lislam_pgo_add_keyframes(lislam_pgo* p, const double* pose7, int32_t n_poses, const int32_t* index, int32_t n,
                              const double* var6) {
   if (!p || n < 0 || n_poses < 0 || (n > 0 && (!pose7 || !index))) return LISLAM_ERR_ARG;
   lislam_ctx* c = p->ctx;
-  if (var6 && !positive(var6, 6)) return gfail(c, LISLAM_ERR_ARG, "lislam_pgo_add_keyframes: variances must be positive");
-  int rc;
-  if ((rc = check_index(c, "lislam_pgo_add_keyframes", "index", index, n, n_poses))) return rc;
+  if (var6 && !positive(var6, 6)) return fail(c, LISLAM_ERR_ARG, "lislam_pgo_add_keyframes: variances must be positive");
+  LISLAM_RC(check_index(c, "lislam_pgo_add_keyframes", "index", index, n, n_poses, true));
   if (n == 0) return LISLAM_OK;
   return add_keyframes(p, "lislam_pgo_add_keyframes", nullptr, pose7, n_poses, index, n, var6);
 }
@@ -1076,14 +1036,13 @@ int lislam_pgo_add_keyframes(lislam_pgo* p, const double* pose7, int32_t n_poses
 int lislam_pgo_add_batch_scans(lislam_pgo* p, lislam_batch* b, const int32_t* scans, int32_t n, const double* var6) {
   if (!p || !b || n < 0 || (n > 0 && !scans)) return LISLAM_ERR_ARG;
   lislam_ctx* c = p->ctx;
-  if (b->ctx != c) return gfail(c, LISLAM_ERR_ARG, "lislam_pgo_add_batch_scans: the batch belongs to another context");
-  if (var6 && !positive(var6, 6)) return gfail(c, LISLAM_ERR_ARG, "lislam_pgo_add_batch_scans: variances must be positive");
+  LISLAM_RC(check_same_context(c, "lislam_pgo_add_batch_scans", b));
+  if (var6 && !positive(var6, 6)) return fail(c, LISLAM_ERR_ARG, "lislam_pgo_add_batch_scans: variances must be positive");
   if (n > 0 && b->extracted < 1)
-    return gfail(c, LISLAM_ERR_STATE, "lislam_pgo_add_batch_scans: extract the batch and run its odometry first");
-  int rc;
-  if ((rc = check_index(c, "lislam_pgo_add_batch_scans", "scans", scans, n, b->extracted))) return rc;
+    return fail(c, LISLAM_ERR_STATE, "lislam_pgo_add_batch_scans: extract the batch and run its odometry first");
+  LISLAM_RC(check_index(c, "lislam_pgo_add_batch_scans", "scans", scans, n, b->extracted, true));
   if (n == 0) return LISLAM_OK;
-  if ((rc = lislam_batch_settle(b)) != LISLAM_OK) return rc;
+  LISLAM_RC(lislam_batch_settle(b));
   return add_keyframes(p, "lislam_pgo_add_batch_scans", b->oa.pose, nullptr, b->extracted, scans, n, var6);
 }
 
@@ -1091,19 +1050,19 @@ int lislam_pgo_linearize(lislam_pgo* p, double* residual, double* J_from, double
   if (!p) return LISLAM_ERR_ARG;
   lislam_ctx* c = p->ctx;
   int rc;
-  if (p->n == 0) return gfail(c, LISLAM_ERR_STATE, "lislam_pgo_linearize: the graph is empty");
+  if (p->n == 0) return fail(c, LISLAM_ERR_STATE, "lislam_pgo_linearize: the graph is empty");
   if ((rc = ready(p, "lislam_pgo_linearize"))) return rc;
   hipSetDevice(c->device);
   const size_t E = (size_t)p->e;
   launch_linearize<kRaw>(p, p->x[p->cur]);
   hipLaunchKernelGGL(k_pgo_sum, dim3(1), dim3(kThreads), 0, c->stream, p->e + 1, p->b.term, &p->d_res->cost_cur);
-  GCHK(c, hipGetLastError());
-  if (residual) GCHK(c, hipMemcpyAsync(residual, p->b.bt, (E + 1) * 6 * 8, hipMemcpyDeviceToHost, c->stream));
-  if (J_from && E) GCHK(c, hipMemcpyAsync(J_from, p->b.Af, E * 36 * 8, hipMemcpyDeviceToHost, c->stream));
-  if (J_to) GCHK(c, hipMemcpyAsync(J_to, p->b.At, (E + 1) * 36 * 8, hipMemcpyDeviceToHost, c->stream));
-  if (weight) GCHK(c, hipMemcpyAsync(weight, p->b.wt, (E + 1) * 8, hipMemcpyDeviceToHost, c->stream));
-  if (cost) GCHK(c, hipMemcpyAsync(cost, &p->d_res->cost_cur, 8, hipMemcpyDeviceToHost, c->stream));
-  GCHK(c, hipStreamSynchronize(c->stream));
+  LISLAM_HIPCHK(c, hipGetLastError());
+  if (residual) LISLAM_HIPCHK(c, hipMemcpyAsync(residual, p->b.bt, (E + 1) * 6 * 8, hipMemcpyDeviceToHost, c->stream));
+  if (J_from && E) LISLAM_HIPCHK(c, hipMemcpyAsync(J_from, p->b.Af, E * 36 * 8, hipMemcpyDeviceToHost, c->stream));
+  if (J_to) LISLAM_HIPCHK(c, hipMemcpyAsync(J_to, p->b.At, (E + 1) * 36 * 8, hipMemcpyDeviceToHost, c->stream));
+  if (weight) LISLAM_HIPCHK(c, hipMemcpyAsync(weight, p->b.wt, (E + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+  if (cost) LISLAM_HIPCHK(c, hipMemcpyAsync(cost, &p->d_res->cost_cur, 8, hipMemcpyDeviceToHost, c->stream));
+  LISLAM_HIPCHK(c, hipStreamSynchronize(c->stream));
   return LISLAM_OK;
 }
 
@@ -1125,8 +1084,8 @@ int lislam_pgo_optimize(lislam_pgo* p, int32_t* info, double* stats) {
     if (p->cfg.max_iterations == 0) {
       launch_linearize<kCost>(p, p->x[p->cur]);
       hipLaunchKernelGGL(k_pgo_sum, dim3(1), dim3(kThreads), 0, c->stream, E + 1, p->b.term, &p->d_res->cost_cur);
-      GCHK(c, hipMemcpyAsync(p->h_res, p->d_res, sizeof(Result), hipMemcpyDeviceToHost, c->stream));
-      GCHK(c, hipStreamSynchronize(c->stream));
+      LISLAM_HIPCHK(c, hipMemcpyAsync(p->h_res, p->d_res, sizeof(Result), hipMemcpyDeviceToHost, c->stream));
+      LISLAM_HIPCHK(c, hipStreamSynchronize(c->stream));
       cost0 = cost = p->h_res->cost_cur;
     }
     while (iterations < p->cfg.max_iterations) {
@@ -1146,10 +1105,10 @@ int lislam_pgo_optimize(lislam_pgo* p, int32_t* info, double* stats) {
       hipLaunchKernelGGL(k_pgo_retract, dim3((N + kThreads - 1) / kThreads), dim3(kThreads), 0, c->stream, N, xc, p->vec[0], xt);
       launch_linearize<kCost>(p, xt);
       hipLaunchKernelGGL(k_pgo_sum, dim3(1), dim3(kThreads), 0, c->stream, E + 1, p->b.term, &p->d_res->cost_try);
-      GCHK(c, hipGetLastError());
+      LISLAM_HIPCHK(c, hipGetLastError());
       // the iteration's one synchronisation: both costs and the CG summary
-      GCHK(c, hipMemcpyAsync(p->h_res, p->d_res, sizeof(Result), hipMemcpyDeviceToHost, c->stream));
-      GCHK(c, hipStreamSynchronize(c->stream));
+      LISLAM_HIPCHK(c, hipMemcpyAsync(p->h_res, p->d_res, sizeof(Result), hipMemcpyDeviceToHost, c->stream));
+      LISLAM_HIPCHK(c, hipStreamSynchronize(c->stream));
       const Result r = *p->h_res;
       if (iterations == 0) cost0 = cost = r.cost_cur;
       iterations++;
@@ -1186,17 +1145,17 @@ int lislam_pgo_poses(lislam_pgo* p, int32_t first, int32_t n, double* pose7, flo
   if (!p || n < 0) return LISLAM_ERR_ARG;
   lislam_ctx* c = p->ctx;
   if (first < 0 || (int64_t)first + n > p->n)
-    return gfail(c, LISLAM_ERR_ARG, "lislam_pgo_poses: nodes [%d, %d + %d) out of range (size %d)", first, first, n, p->n);
+    return fail(c, LISLAM_ERR_ARG, "lislam_pgo_poses: nodes [%d, %d + %d) out of range (size %d)", first, first, n, p->n);
   if (n == 0) return LISLAM_OK;
   hipSetDevice(c->device);
   const double* src = p->x[p->cur] + (size_t)first * 7;
-  if (pose7) GCHK(c, hipMemcpyAsync(pose7, src, (size_t)n * 7 * 8, hipMemcpyDeviceToHost, c->stream));
+  if (pose7) LISLAM_HIPCHK(c, hipMemcpyAsync(pose7, src, (size_t)n * 7 * 8, hipMemcpyDeviceToHost, c->stream));
   if (pose6d) {
     hipLaunchKernelGGL(k_pgo_pose6d, dim3((n + kThreads - 1) / kThreads), dim3(kThreads), 0, c->stream, n, src, p->p6);
-    GCHK(c, hipGetLastError());
-    GCHK(c, hipMemcpyAsync(pose6d, p->p6, (size_t)n * 6 * 4, hipMemcpyDeviceToHost, c->stream));
+    LISLAM_HIPCHK(c, hipGetLastError());
+    LISLAM_HIPCHK(c, hipMemcpyAsync(pose6d, p->p6, (size_t)n * 6 * 4, hipMemcpyDeviceToHost, c->stream));
   }
-  GCHK(c, hipStreamSynchronize(c->stream));
+  LISLAM_HIPCHK(c, hipStreamSynchronize(c->stream));
   return LISLAM_OK;
 }
 
@@ -1206,16 +1165,16 @@ int lislam_pgo_edges(lislam_pgo* p, int32_t first, int32_t n, int32_t* from, int
   if (!p || n < 0) return LISLAM_ERR_ARG;
   lislam_ctx* c = p->ctx;
   if (first < 0 || (int64_t)first + n > p->e)
-    return gfail(c, LISLAM_ERR_ARG, "lislam_pgo_edges: edges [%d, %d + %d) out of range (size %d)", first, first, n, p->e);
+    return fail(c, LISLAM_ERR_ARG, "lislam_pgo_edges: edges [%d, %d + %d) out of range (size %d)", first, first, n, p->e);
   if (n == 0) return LISLAM_OK;
   hipSetDevice(c->device);
   const size_t at = (size_t)first, N = (size_t)n;
-  if (from) GCHK(c, hipMemcpyAsync(from, p->from + at, N * 4, hipMemcpyDeviceToHost, c->stream));
-  if (to) GCHK(c, hipMemcpyAsync(to, p->to + at, N * 4, hipMemcpyDeviceToHost, c->stream));
-  if (robust) GCHK(c, hipMemcpyAsync(robust, p->robust + at, N * 4, hipMemcpyDeviceToHost, c->stream));
-  if (meas7) GCHK(c, hipMemcpyAsync(meas7, p->meas + at * 7, N * 7 * 8, hipMemcpyDeviceToHost, c->stream));
-  if (var6) GCHK(c, hipMemcpyAsync(var6, p->sigma + at * 6, N * 6 * 8, hipMemcpyDeviceToHost, c->stream));
-  GCHK(c, hipStreamSynchronize(c->stream));
+  if (from) LISLAM_HIPCHK(c, hipMemcpyAsync(from, p->from + at, N * 4, hipMemcpyDeviceToHost, c->stream));
+  if (to) LISLAM_HIPCHK(c, hipMemcpyAsync(to, p->to + at, N * 4, hipMemcpyDeviceToHost, c->stream));
+  if (robust) LISLAM_HIPCHK(c, hipMemcpyAsync(robust, p->robust + at, N * 4, hipMemcpyDeviceToHost, c->stream));
+  if (meas7) LISLAM_HIPCHK(c, hipMemcpyAsync(meas7, p->meas + at * 7, N * 7 * 8, hipMemcpyDeviceToHost, c->stream));
+  if (var6) LISLAM_HIPCHK(c, hipMemcpyAsync(var6, p->sigma + at * 6, N * 6 * 8, hipMemcpyDeviceToHost, c->stream));
+  LISLAM_HIPCHK(c, hipStreamSynchronize(c->stream));
   if (var6)
     for (size_t k = 0; k < N * 6; k++) var6[k] = var6[k] * var6[k];
   return LISLAM_OK;

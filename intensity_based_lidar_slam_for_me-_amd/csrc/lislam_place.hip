@@ -40,6 +40,7 @@
 #include "lislam_batch.hpp"
 #include "lislam_ctx.hpp"
 #include "lislam_device.hpp"
+#include "lislam_host.hpp"
 
 namespace lislam {
 namespace place {
@@ -346,6 +347,7 @@ __global__ __launch_bounds__(kThreads) void k_sc_detect(Params P, Db db, int fir
 }  // namespace lislam
 
 using namespace lislam::place;
+using namespace lislam;
 
 struct lislam_place {
   lislam_ctx* ctx = nullptr;
@@ -357,50 +359,14 @@ struct lislam_place {
   double* skey = nullptr;
   double* cnorm = nullptr;
   // grow-only staging: packed points and their per-cloud (offset, count); detect / distance results
-  void* stage = nullptr;
-  size_t stage_bytes = 0;
-  void* meta = nullptr;
-  size_t meta_bytes = 0;
-  void* res = nullptr;
-  size_t res_bytes = 0;
+  lislam::DBuf stage, meta, res;
   Db db() const { return Db{desc, rkey, skey, cnorm}; }
 };
 
 namespace {
 
-int pfail(lislam_ctx* c, int code, const char* fmt, ...) {
-  if (c) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    c->err = buf;
-  }
-  return code;
-}
-
-#define PCHK(ctx, x)                                                                                  \
-  do {                                                                                                \
-    hipError_t e_ = (x);                                                                              \
-    if (e_ != hipSuccess) return pfail(ctx, LISLAM_ERR_DEVICE, "%s: %s", #x, hipGetErrorString(e_)); \
-  } while (0)
-
-int reserve(lislam_ctx* c, void** p, size_t* have, size_t want) {
-  if (want <= *have) return LISLAM_OK;
-  if (*p) {
-    PCHK(c, hipStreamSynchronize(c->stream));
-    (void)hipFree(*p);
-    *p = nullptr;
-    *have = 0;
-  }
-  PCHK(c, hipMalloc(p, want));
-  *have = want;
-  return LISLAM_OK;
-}
-
 void free_place(lislam_place* p) {
-  for (void* q : {(void*)p->keys, (void*)p->desc, (void*)p->rkey, (void*)p->skey, (void*)p->cnorm, p->stage, p->meta, p->res})
+  for (void* q : {(void*)p->keys, (void*)p->desc, (void*)p->rkey, (void*)p->skey, (void*)p->cnorm})
     if (q) (void)hipFree(q);
   delete p;
 }
@@ -413,7 +379,7 @@ int describe(lislam_place* p, const Clouds& cl, int n_clouds) {
                      p->keys + (size_t)p->n * bins);
   hipLaunchKernelGGL(k_sc_finish, dim3(n_clouds), dim3(kThreads), 0, c->stream, p->P, p->n, p->keys, p->desc, p->rkey, p->skey,
                      p->cnorm);
-  PCHK(c, hipGetLastError());
+  LISLAM_HIPCHK(c, hipGetLastError());
   p->n += n_clouds;
   return LISLAM_OK;
 }
@@ -431,11 +397,11 @@ int lislam_place_create(lislam_ctx* c, const lislam_place_config* cfg, int32_t c
   if (cfg) d = *cfg;
   if (d.num_ring < 1 || d.num_ring > kMaxRing || d.num_sector < 1 || d.num_sector > kMaxSector || d.num_candidates < 1 ||
       d.num_candidates > kMaxCand)
-    return pfail(c, LISLAM_ERR_ARG, "lislam_place_create: num_ring 1..%d, num_sector 1..%d, num_candidates 1..%d", kMaxRing,
-                 kMaxSector, kMaxCand);
+    return fail(c, LISLAM_ERR_ARG, "lislam_place_create: num_ring 1..%d, num_sector 1..%d, num_candidates 1..%d", kMaxRing,
+                kMaxSector, kMaxCand);
   if (!(d.max_radius > 0) || !std::isfinite(d.max_radius) || !std::isfinite(d.lidar_height) || !(d.search_ratio >= 0) ||
       !(d.search_ratio <= 1e6) || d.num_exclude_recent < 0 || d.tree_making_period < 1 || capacity < 1)
-    return pfail(c, LISLAM_ERR_ARG, "lislam_place_create: invalid configuration or capacity");
+    return fail(c, LISLAM_ERR_ARG, "lislam_place_create: invalid configuration or capacity");
   hipSetDevice(c->device);
   lislam_place* p = new lislam_place();
   p->ctx = c;
@@ -454,7 +420,7 @@ int lislam_place_create(lislam_ctx* c, const lislam_place_config* cfg, int32_t c
   if (!ok) {
     (void)hipGetLastError();
     free_place(p);
-    return pfail(c, LISLAM_ERR_DEVICE, "lislam_place_create: device allocation failed");
+    return fail(c, LISLAM_ERR_DEVICE, "lislam_place_create: device allocation failed");
   }
   *out = p;
   return LISLAM_OK;
@@ -481,48 +447,43 @@ int lislam_place_add_clouds(lislam_place* p, const void* points, const int32_t* 
   int64_t total = 0;
   int max_count = 0;
   for (int k = 0; k < n_clouds; k++) {
-    if (counts[k] < 0) return pfail(c, LISLAM_ERR_ARG, "lislam_place_add_clouds: counts[%d] = %d", k, counts[k]);
+    if (counts[k] < 0) return fail(c, LISLAM_ERR_ARG, "lislam_place_add_clouds: counts[%d] = %d", k, counts[k]);
     total += counts[k];
     max_count = std::max(max_count, counts[k]);
   }
-  if (total > 0 && !points) return pfail(c, LISLAM_ERR_ARG, "lislam_place_add_clouds: null points");
-  if (total > 0x3fffffff) return pfail(c, LISLAM_ERR_CAPACITY, "lislam_place_add_clouds: clouds too large");
+  if (total > 0 && !points) return fail(c, LISLAM_ERR_ARG, "lislam_place_add_clouds: null points");
+  if (total > 0x3fffffff) return fail(c, LISLAM_ERR_CAPACITY, "lislam_place_add_clouds: clouds too large");
   if ((int64_t)p->n + n_clouds > p->capacity)
-    return pfail(c, LISLAM_ERR_CAPACITY, "lislam_place_add_clouds: %d + %d entries exceed the capacity %d", p->n, n_clouds,
-                 p->capacity);
+    return fail(c, LISLAM_ERR_CAPACITY, "lislam_place_add_clouds: %d + %d entries exceed the capacity %d", p->n, n_clouds,
+                p->capacity);
   hipSetDevice(c->device);
-  int rc;
-  if ((rc = reserve(c, &p->stage, &p->stage_bytes, (size_t)std::max<int64_t>(total, 1) * 16))) return rc;
-  const size_t meta = (size_t)n_clouds * (sizeof(long long) + sizeof(int));
-  if ((rc = reserve(c, &p->meta, &p->meta_bytes, meta))) return rc;
+  LISLAM_HIPCHK(c, p->stage.reserve((size_t)std::max<int64_t>(total, 1) * 16, c->stream));
+  LISLAM_HIPCHK(c, p->meta.reserve((size_t)n_clouds * (sizeof(long long) + sizeof(int)), c->stream));
   std::vector<long long> off(n_clouds);
   long long run = 0;
   for (int k = 0; k < n_clouds; k++) { off[k] = run; run += counts[k]; }
-  long long* d_off = static_cast<long long*>(p->meta);
+  long long* d_off = p->meta.as<long long>();
   int* d_cnt = reinterpret_cast<int*>(d_off + n_clouds);
   // pageable sources: these copies have read them when they return
-  PCHK(c, hipMemcpyAsync(d_off, off.data(), (size_t)n_clouds * sizeof(long long), hipMemcpyHostToDevice, c->stream));
-  PCHK(c, hipMemcpyAsync(d_cnt, counts, (size_t)n_clouds * sizeof(int), hipMemcpyHostToDevice, c->stream));
-  if (total) PCHK(c, hipMemcpyAsync(p->stage, points, (size_t)total * 16, hipMemcpyDefault, c->stream));
-  Clouds cl{static_cast<const float4*>(p->stage), d_off, d_cnt, 0, blocks_for(max_count)};
-  if ((rc = describe(p, cl, n_clouds))) return rc;
+  LISLAM_HIPCHK(c, hipMemcpyAsync(d_off, off.data(), (size_t)n_clouds * sizeof(long long), hipMemcpyHostToDevice, c->stream));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(d_cnt, counts, (size_t)n_clouds * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  if (total) LISLAM_HIPCHK(c, hipMemcpyAsync(p->stage.p, points, (size_t)total * 16, hipMemcpyDefault, c->stream));
+  Clouds cl{p->stage.as<const float4>(), d_off, d_cnt, 0, blocks_for(max_count)};
+  LISLAM_RC(describe(p, cl, n_clouds));
   // the host arrays above leave scope: the copies that read them must have run
-  PCHK(c, hipStreamSynchronize(c->stream));
+  LISLAM_HIPCHK(c, hipStreamSynchronize(c->stream));
   return LISLAM_OK;
 }
 
 int lislam_place_add_batch(lislam_place* p, lislam_batch* b, int32_t first_scan, int32_t n_scans) {
   if (!p || !b) return LISLAM_ERR_ARG;
   lislam_ctx* c = p->ctx;
-  if (b->ctx != c) return pfail(c, LISLAM_ERR_ARG, "lislam_place_add_batch: the batch belongs to another context");
-  if (first_scan < 0 || n_scans < 0 || (int64_t)first_scan + n_scans > b->max_scans)
-    return pfail(c, LISLAM_ERR_ARG, "lislam_place_add_batch: scans [%d, %d + %d) out of range", first_scan, first_scan, n_scans);
-  if (!b->fa.track) return pfail(c, LISLAM_ERR_STATE, "lislam_place_add_batch: cloud_track not materialized (want_images=0)");
-  if (first_scan + n_scans > b->extracted)
-    return pfail(c, LISLAM_ERR_STATE, "lislam_place_add_batch: extract %d scans first", first_scan + n_scans);
-  if ((int64_t)p->n + n_scans > p->capacity)
-    return pfail(c, LISLAM_ERR_CAPACITY, "lislam_place_add_batch: %d + %d entries exceed the capacity %d", p->n, n_scans,
-                 p->capacity);
+  const char* who = "lislam_place_add_batch";
+  LISLAM_RC(check_same_context(c, who, b));
+  LISLAM_RC(check_scan_range(c, who, b, first_scan, n_scans));
+  LISLAM_RC(check_cloud_track(c, who, b));
+  LISLAM_RC(check_extracted(c, who, b, first_scan, n_scans));
+  LISLAM_RC(check_capacity(c, who, p->n, n_scans, "entries", p->capacity));
   if (n_scans == 0) return LISLAM_OK;
   hipSetDevice(c->device);
   Clouds cl{reinterpret_cast<const float4*>(b->fa.track) + (size_t)first_scan * b->N, nullptr, nullptr, b->N, blocks_for(b->N)};
@@ -532,32 +493,28 @@ int lislam_place_add_batch(lislam_place* p, lislam_batch* b, int32_t first_scan,
 int lislam_place_add_batch_scans(lislam_place* p, lislam_batch* b, const int32_t* scans, int32_t n) {
   if (!p || !b || n < 0 || (n > 0 && !scans)) return LISLAM_ERR_ARG;
   lislam_ctx* c = p->ctx;
-  if (b->ctx != c) return pfail(c, LISLAM_ERR_ARG, "lislam_place_add_batch_scans: the batch belongs to another context");
-  if (!b->fa.track) return pfail(c, LISLAM_ERR_STATE, "lislam_place_add_batch_scans: cloud_track not materialized (want_images=0)");
-  if (n > 0 && b->extracted < 1) return pfail(c, LISLAM_ERR_STATE, "lislam_place_add_batch_scans: extract the batch first");
-  for (int k = 0; k < n; k++)
-    if (scans[k] < 0 || scans[k] >= b->extracted)
-      return pfail(c, LISLAM_ERR_ARG, "lislam_place_add_batch_scans: scans[%d] = %d outside [0, %d)", k, scans[k], b->extracted);
-  if ((int64_t)p->n + n > p->capacity)
-    return pfail(c, LISLAM_ERR_CAPACITY, "lislam_place_add_batch_scans: %d + %d entries exceed the capacity %d", p->n, n,
-                 p->capacity);
+  const char* who = "lislam_place_add_batch_scans";
+  LISLAM_RC(check_same_context(c, who, b));
+  LISLAM_RC(check_cloud_track(c, who, b));
+  LISLAM_RC(check_extracted_any(c, who, b, n));
+  LISLAM_RC(check_index(c, who, "scans", scans, n, b->extracted, false));
+  LISLAM_RC(check_capacity(c, who, p->n, n, "entries", p->capacity));
   if (n == 0) return LISLAM_OK;
   hipSetDevice(c->device);
-  int rc;
-  if ((rc = reserve(c, &p->meta, &p->meta_bytes, (size_t)n * (sizeof(long long) + sizeof(int))))) return rc;
+  LISLAM_HIPCHK(c, p->meta.reserve((size_t)n * (sizeof(long long) + sizeof(int)), c->stream));
   // cloud k = scan scans[k]: the packed form's (offset, count) pairs over the batch's cloud_track
   std::vector<long long> off(n);
   std::vector<int> cnt(n, b->N);
   for (int k = 0; k < n; k++) off[k] = (long long)scans[k] * b->N;
-  long long* d_off = static_cast<long long*>(p->meta);
+  long long* d_off = p->meta.as<long long>();
   int* d_cnt = reinterpret_cast<int*>(d_off + n);
   // pageable sources: these copies have read them when they return
-  PCHK(c, hipMemcpyAsync(d_off, off.data(), (size_t)n * sizeof(long long), hipMemcpyHostToDevice, c->stream));
-  PCHK(c, hipMemcpyAsync(d_cnt, cnt.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(d_off, off.data(), (size_t)n * sizeof(long long), hipMemcpyHostToDevice, c->stream));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(d_cnt, cnt.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, c->stream));
   Clouds cl{reinterpret_cast<const float4*>(b->fa.track), d_off, d_cnt, 0, blocks_for(b->N)};
-  if ((rc = describe(p, cl, n))) return rc;
+  LISLAM_RC(describe(p, cl, n));
   // the host arrays above leave scope: the copies that read them must have run
-  PCHK(c, hipStreamSynchronize(c->stream));
+  LISLAM_HIPCHK(c, hipStreamSynchronize(c->stream));
   return LISLAM_OK;
 }
 
@@ -566,27 +523,26 @@ int lislam_place_detect(lislam_place* p, int32_t first, int32_t n, int32_t* loop
   if (!p || n < 0) return LISLAM_ERR_ARG;
   lislam_ctx* c = p->ctx;
   if (first < 0 || (int64_t)first + n > p->n)
-    return pfail(c, LISLAM_ERR_ARG, "lislam_place_detect: keyframes [%d, %d + %d) out of range (size %d)", first, first, n, p->n);
+    return fail(c, LISLAM_ERR_ARG, "lislam_place_detect: keyframes [%d, %d + %d) out of range (size %d)", first, first, n, p->n);
   if (n == 0) return LISLAM_OK;
   hipSetDevice(c->device);
-  int rc;
   const size_t N = (size_t)n;
-  if ((rc = reserve(c, &p->res, &p->res_bytes, N * 24))) return rc;
+  LISLAM_HIPCHK(c, p->res.reserve(N * 24, c->stream));
   // [min_dist double][loop_id][yaw][nn_idx][nn_align]
-  double* d_dist = static_cast<double*>(p->res);
+  double* d_dist = p->res.as<double>();
   int* d_loop = reinterpret_cast<int*>(d_dist + N);
   float* d_yaw = reinterpret_cast<float*>(d_loop + N);
   int* d_idx = reinterpret_cast<int*>(d_yaw + N);
   int* d_align = d_idx + N;
   hipLaunchKernelGGL(k_sc_detect, dim3(n), dim3(kThreads), 0, c->stream, p->P, p->db(), first,
                      DetectOut{d_loop, d_yaw, d_dist, d_idx, d_align});
-  PCHK(c, hipGetLastError());
-  if (loop_id) PCHK(c, hipMemcpyAsync(loop_id, d_loop, N * 4, hipMemcpyDeviceToHost, c->stream));
-  if (yaw) PCHK(c, hipMemcpyAsync(yaw, d_yaw, N * 4, hipMemcpyDeviceToHost, c->stream));
-  if (min_dist) PCHK(c, hipMemcpyAsync(min_dist, d_dist, N * 8, hipMemcpyDeviceToHost, c->stream));
-  if (nn_idx) PCHK(c, hipMemcpyAsync(nn_idx, d_idx, N * 4, hipMemcpyDeviceToHost, c->stream));
-  if (nn_align) PCHK(c, hipMemcpyAsync(nn_align, d_align, N * 4, hipMemcpyDeviceToHost, c->stream));
-  PCHK(c, hipStreamSynchronize(c->stream));
+  LISLAM_HIPCHK(c, hipGetLastError());
+  if (loop_id) LISLAM_HIPCHK(c, hipMemcpyAsync(loop_id, d_loop, N * 4, hipMemcpyDeviceToHost, c->stream));
+  if (yaw) LISLAM_HIPCHK(c, hipMemcpyAsync(yaw, d_yaw, N * 4, hipMemcpyDeviceToHost, c->stream));
+  if (min_dist) LISLAM_HIPCHK(c, hipMemcpyAsync(min_dist, d_dist, N * 8, hipMemcpyDeviceToHost, c->stream));
+  if (nn_idx) LISLAM_HIPCHK(c, hipMemcpyAsync(nn_idx, d_idx, N * 4, hipMemcpyDeviceToHost, c->stream));
+  if (nn_align) LISLAM_HIPCHK(c, hipMemcpyAsync(nn_align, d_align, N * 4, hipMemcpyDeviceToHost, c->stream));
+  LISLAM_HIPCHK(c, hipStreamSynchronize(c->stream));
   return LISLAM_OK;
 }
 
@@ -595,23 +551,22 @@ int lislam_place_distance(lislam_place* p, const int32_t* a, const int32_t* b, i
   lislam_ctx* c = p->ctx;
   for (int k = 0; k < n_pairs; k++)
     if (a[k] < 0 || a[k] >= p->n || b[k] < 0 || b[k] >= p->n)
-      return pfail(c, LISLAM_ERR_ARG, "lislam_place_distance: pair %d = (%d, %d) out of range (size %d)", k, a[k], b[k], p->n);
+      return fail(c, LISLAM_ERR_ARG, "lislam_place_distance: pair %d = (%d, %d) out of range (size %d)", k, a[k], b[k], p->n);
   if (n_pairs == 0) return LISLAM_OK;
   hipSetDevice(c->device);
-  int rc;
   const size_t N = (size_t)n_pairs;
-  if ((rc = reserve(c, &p->res, &p->res_bytes, N * 24))) return rc;
-  double* d_dist = static_cast<double*>(p->res);
+  LISLAM_HIPCHK(c, p->res.reserve(N * 24, c->stream));
+  double* d_dist = p->res.as<double>();
   int* d_shift = reinterpret_cast<int*>(d_dist + N);
   int* d_a = d_shift + N;
   int* d_b = d_a + N;
-  PCHK(c, hipMemcpyAsync(d_a, a, N * 4, hipMemcpyHostToDevice, c->stream));
-  PCHK(c, hipMemcpyAsync(d_b, b, N * 4, hipMemcpyHostToDevice, c->stream));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(d_a, a, N * 4, hipMemcpyHostToDevice, c->stream));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(d_b, b, N * 4, hipMemcpyHostToDevice, c->stream));
   hipLaunchKernelGGL(k_sc_distance, dim3(n_pairs), dim3(64), 0, c->stream, p->P, p->db(), d_a, d_b, d_dist, d_shift);
-  PCHK(c, hipGetLastError());
-  if (dist) PCHK(c, hipMemcpyAsync(dist, d_dist, N * 8, hipMemcpyDeviceToHost, c->stream));
-  if (shift) PCHK(c, hipMemcpyAsync(shift, d_shift, N * 4, hipMemcpyDeviceToHost, c->stream));
-  PCHK(c, hipStreamSynchronize(c->stream));
+  LISLAM_HIPCHK(c, hipGetLastError());
+  if (dist) LISLAM_HIPCHK(c, hipMemcpyAsync(dist, d_dist, N * 8, hipMemcpyDeviceToHost, c->stream));
+  if (shift) LISLAM_HIPCHK(c, hipMemcpyAsync(shift, d_shift, N * 4, hipMemcpyDeviceToHost, c->stream));
+  LISLAM_HIPCHK(c, hipStreamSynchronize(c->stream));
   return LISLAM_OK;
 }
 
@@ -619,7 +574,7 @@ int lislam_place_download(lislam_place* p, int32_t what, int32_t index, void* ds
   if (!p || !dst || cap < 0) return LISLAM_ERR_ARG;
   lislam_ctx* c = p->ctx;
   if (index < 0 || index >= p->n)
-    return pfail(c, LISLAM_ERR_ARG, "lislam_place_download: index %d out of range (size %d)", index, p->n);
+    return fail(c, LISLAM_ERR_ARG, "lislam_place_download: index %d out of range (size %d)", index, p->n);
   const void* src;
   int cnt;
   size_t esz;
@@ -627,13 +582,13 @@ int lislam_place_download(lislam_place* p, int32_t what, int32_t index, void* ds
     case LISLAM_PLACE_DESC: cnt = p->P.R * p->P.S; esz = 8; src = p->desc + (size_t)index * cnt; break;
     case LISLAM_PLACE_RING_KEY: cnt = p->P.R; esz = 4; src = p->rkey + (size_t)index * cnt; break;
     case LISLAM_PLACE_SECTOR_KEY: cnt = p->P.S; esz = 8; src = p->skey + (size_t)index * cnt; break;
-    default: return pfail(c, LISLAM_ERR_ARG, "lislam_place_download: unknown output %d", what);
+    default: return fail(c, LISLAM_ERR_ARG, "lislam_place_download: unknown output %d", what);
   }
   if (n) *n = cnt;
-  if (cap < cnt) return pfail(c, LISLAM_ERR_CAPACITY, "lislam_place_download: %d elements, capacity %d", cnt, cap);
+  if (cap < cnt) return fail(c, LISLAM_ERR_CAPACITY, "lislam_place_download: %d elements, capacity %d", cnt, cap);
   hipSetDevice(c->device);
-  PCHK(c, hipMemcpyAsync(dst, src, (size_t)cnt * esz, hipMemcpyDeviceToHost, c->stream));
-  PCHK(c, hipStreamSynchronize(c->stream));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(dst, src, (size_t)cnt * esz, hipMemcpyDeviceToHost, c->stream));
+  LISLAM_HIPCHK(c, hipStreamSynchronize(c->stream));
   return LISLAM_OK;
 }
 
