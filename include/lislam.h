@@ -361,7 +361,13 @@ int lislam_eval_factors_raw(lislam_ctx* ctx, int32_t n, const int32_t* kind, con
  * blocked; null = none) + extractPointsAndFilterZeroValue + compute on one intensity image
  * (intensity_feature_tracker.cpp:609-628, :1071-1099).  kp[n][6] = x, y, size, angle (deg),
  * response, octave; desc[n][32]; p3d[n][4] = the cloud_track point (x, y, z, 0).  cloud_track is
- * the organized H*W float4 cloud of ImageHandler::cloud_handler.  Host or device pointers. */
+ * the organized H*W float4 cloud of ImageHandler::cloud_handler.  Host or device pointers.
+ * H, W >= 8, nfeatures 1..16384.
+ * Capacity: pyramid level l, whose share of the budget is n_l (nfeaturesPerLevel), keeps at most
+ * 2 * n_l + 64 keypoints.  The reference is unbounded there: KeyPointsFilter::retainBest keeps every
+ * response tied with the n_l-th, so an image that repeats a pattern can carry a level past any
+ * fixed room.  Beyond it the call fails with LISLAM_ERR_CAPACITY (lislam_last_error names the ORB
+ * level keypoint capacity) and returns no keypoints; it never returns a cut set. */
 int lislam_orb_detect(lislam_ctx* ctx, const uint8_t* image, const float* cloud_track, const uint8_t* mask, int32_t H,
                       int32_t W, int32_t nfeatures, float* kp, uint8_t* desc, float* p3d, int32_t cap, int32_t* n);
 /* BFMatcher(NORM_HAMMING, crossCheck=true).match(query, train) (:631): matches[m][3] = query,
@@ -371,7 +377,10 @@ int lislam_orb_match(lislam_ctx* ctx, const uint8_t* qdesc, int32_t nq, const ui
 /* feature_tracker::detectfeatures (intensity_feature_tracker.cpp:597-738): one frame per step,
  * state = the previous frame.  T_s2s[7] = (q x,y,z,w, t) of p2p_calculateRandT (identity when
  * the frame is skipped); stats[8] = good (1) / skipped (0) / first frame (-1), re-detected,
- * keypoints, matches, good matches, LM iterations, LM termination, previous keypoints. */
+ * keypoints, matches, good matches, LM iterations, LM termination, previous keypoints.
+ * A frame one of whose levels outgrows the capacity of lislam_orb_detect (2 * n_l + 64 keypoints,
+ * in its n-feature or its 2n-feature detection) fails the step with LISLAM_ERR_CAPACITY; T_s2s and
+ * stats are not written, the frame is not kept, and the next frame is treated as a first frame. */
 typedef struct lislam_intensity_tracker lislam_intensity_tracker;
 int lislam_intensity_tracker_create(lislam_ctx* ctx, int32_t H, int32_t W, int32_t nfeatures, const uint8_t* mask,
                                     lislam_intensity_tracker** out);
@@ -383,7 +392,13 @@ int lislam_intensity_tracker_step(lislam_intensity_tracker* t, const uint8_t* im
  * it returns once its work is queued (on a side stream the context stream then waits for); the
  * sequential re-detection rule (intensity_feature_tracker.cpp:652-687) is decided on the device in
  * LISLAM_ORB_ROUNDS passes (default 1).  Reading an ORB output first checks that the device
- * decision converged, and redoes the batch with host-decided rounds if it did not. */
+ * decision converged, and redoes the batch with host-decided rounds if it did not.
+ * Capacity: a scan one of whose levels outgrows the room of lislam_orb_detect (2 * n_l + 64
+ * keypoints; the reference is unbounded), in its n-feature or a 2n-feature detection, fails the
+ * batch with LISLAM_ERR_CAPACITY.  The call is asynchronous, so the failure is reported where the
+ * batch's ORB outputs are first brought to the host: every lislam_batch_download of a
+ * LISLAM_OUT_ORB_* output (and every other reader of the batch's ORB sets) fails with it until the
+ * next lislam_batch_intensity_odometry, which starts clean. */
 int lislam_batch_intensity_odometry(lislam_batch* b, int32_t n_scans, int32_t nfeatures, const uint8_t* mask);
 /* The last lislam_batch_intensity_odometry's cascade, after its outputs were read: info[0] = 1
  * device-decided and converged, 0 redone with host rounds, -1 host rounds from the start
@@ -528,7 +543,7 @@ int lislam_mapopt_step_window(lislam_map* m, lislam_map* corner_map, lislam_mapw
                               const double* odom, double* state, double* out_pose, int32_t* summary);
 /* lislam_orb_detect with mapOptimization's extractPointsAndFilterZeroValue (mapOptimization.cpp:
  * 604-632): a keypoint is dropped only when |x|, |y| and |z| of its point are all below 0.01
- * (the feature tracker's drops on |x| alone). */
+ * (the feature tracker's drops on |x| alone).  The same level capacity and LISLAM_ERR_CAPACITY. */
 int lislam_orb_detect_map(lislam_ctx* ctx, const uint8_t* image, const float* cloud_track, const uint8_t* mask,
                           int32_t H, int32_t W, int32_t nfeatures, float* kp, uint8_t* desc, float* p3d, int32_t cap,
                           int32_t* n);

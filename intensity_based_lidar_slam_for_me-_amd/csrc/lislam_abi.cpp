@@ -939,6 +939,7 @@ static int output_source(lislam_batch* b, int what, int scan, const void** src_o
     case LISLAM_OUT_ORB_POINTS:
     case LISLAM_OUT_ORB_DESCRIPTORS: {
       const int rc = lislam_orb_batch_output(b, what, scan, &src, &cnt, &esz);
+      if (rc == LISLAM_ERR_CAPACITY) return rc;  // a level outgrew its room: the ORB code said which call
       if (rc) return fail(c, rc, "ORB output %d unavailable (run lislam_batch_intensity_odometry first)", what);
       break;
     }

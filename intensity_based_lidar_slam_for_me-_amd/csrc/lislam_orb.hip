@@ -116,6 +116,8 @@ struct Geom {
   int rband[kL + 1];  // prefix of ROI blur bands (kRoiBand ROI rows) per level
 };
 
+constexpr int kLevelOver = 1 << 30;  // flag bit of Args::lcnt
+
 struct Tabs {  // resize coefficients of level l from level l-1 (l >= 1), per axis
   const int* xo; const uint16_t* xc; const int* yo; const uint16_t* yc;
   const int* lim;  // [kL][4] xmin, xmax, ymin, ymax
@@ -135,12 +137,12 @@ struct Args {
   int* cand;              // [S][pix[kL]] candidate pixel indices
   float* cresp;           // [S][pix[kL]]
   float* lkp;             // [S][cap][6] per-level staging (level l at lofs[l])
-  int* lcnt;              // [S][kL]
+  int* lcnt;              // [S][kL] keypoints kept per level; | kLevelOver when the level was cut to lcap
   float* kp;              // [S][cap][6] x, y, size, angle, response, octave
   float4* p3d;            // [S][cap]
   uint8_t* desc;          // [S][cap][32]
   int* nkp;               // [S]
-  int* overflow;          // [1]
+  int* ovf;               // [S] 1 when a level of the scan was cut to lcap (k_orb_finish, every run)
   const int* smap;        // scan of each grid scan index (null: identity from the slot base)
   const int* scount;      // device count of grid scan indices in use (null: all); the rest exit
   int map_filter;         // k_orb_finish's zero filter: 0 feature tracker's, 1 mapOptimization's
@@ -1133,10 +1135,11 @@ __device__ __forceinline__ void orb_select_body(const Args& a, int gi, int l) {
   }
   __syncthreads();
   SEL_PHASE(3);
-  if (n > g.lcap[l]) {
-    if (threadIdx.x == 0) atomicOr(a.overflow, 1);
-    n = g.lcap[l];
-  }
+  // retainBest keeps every response tied with the n-th, so a level can outgrow any fixed room: the
+  // level is cut and marked, k_orb_finish turns the mark into the scan's flag, and every caller
+  // fails with LISLAM_ERR_CAPACITY instead of handing the cut set on
+  const bool over = n > g.lcap[l];
+  if (over) n = g.lcap[l];
   // 5. intensity-centroid angle: one wavefront per 4 keypoints over the circular patch (integer
   //    moments, order-free), fastAtan2 on lane 0; per-level staging
   float* out = a.lkp + ((size_t)s * g.cap + g.lofs[l]) * 6;
@@ -1222,7 +1225,7 @@ __device__ __forceinline__ void orb_select_body(const Args& a, int gi, int l) {
     }
   }
   SEL_PHASE(4);
-  if (threadIdx.x == 0) a.lcnt[s * kL + l] = n;
+  if (threadIdx.x == 0) a.lcnt[s * kL + l] = over ? n | kLevelOver : n;
 }
 
 // Level-major blocks: consecutive blocks (dealt round-robin to the XCDs) are different scans of one
@@ -1249,9 +1252,11 @@ __device__ __forceinline__ void orb_finish_body(const Args& a, int gi) {
   __shared__ SelShared sh;
   const Geom& g = a.g;
   const int s = a.smap ? a.smap[gi] : gi;
-  int n = 0;
+  int n = 0, over = 0;
   for (int l = 0; l < kL; l++) {
-    const int cnt = a.lcnt[s * kL + l];
+    const int raw = a.lcnt[s * kL + l];
+    const int cnt = raw & ~kLevelOver;
+    over |= raw & kLevelOver;
     const float* in = a.lkp + ((size_t)s * g.cap + g.lofs[l]) * 6;
     for (int b0 = 0; b0 < cnt; b0 += blockDim.x) {
       const int i = b0 + threadIdx.x;
@@ -1279,7 +1284,10 @@ __device__ __forceinline__ void orb_finish_body(const Args& a, int gi) {
       n += tot;
     }
   }
-  if (threadIdx.x == 0) a.nkp[s] = n;
+  if (threadIdx.x == 0) {
+    a.nkp[s] = n;
+    a.ovf[s] = over ? 1 : 0;
+  }
 }
 
 __global__ __launch_bounds__(256) void k_orb_finish(Args a) {
@@ -1666,7 +1674,20 @@ struct OutArgs {
   int* outS; double* outT;
   const int* stats; const double* T; const int* redet; const int* nkp0;
   int n_scans;
+  // the device cascade's capacity verdict (orb_out_capacity): the n sets' flags, the 2n sets' flags
+  // of the frames that detected one, and where the verdict goes (null: the host gathers it)
+  const int* ovf1 = nullptr; const int* ovf2 = nullptr; const int8_t* have2 = nullptr;
+  int* over = nullptr;
 };
+
+// (256 threads, all of them) *a.over = some scan's n set, or a 2n set this batch detected, was cut
+__device__ __forceinline__ void orb_out_capacity(const OutArgs& a) {
+  if (!a.over) return;
+  int v = 0;
+  for (int k = threadIdx.x; k < a.n_scans; k += 256) v |= a.ovf1[k] | (a.have2[k] ? a.ovf2[k] : 0);
+  const int any = __syncthreads_or(v);
+  if (threadIdx.x == 0) *a.over = any ? 1 : 0;
+}
 
 __device__ __forceinline__ void orb_out_at(const OutArgs& a, int k) {
   int* outS = a.outS;
@@ -1713,7 +1734,7 @@ struct CascadeArgs {
                       // (each [3][n]: query scans | train scans | slots, stride n)
   int* pcnt;          // [2]
   int* redet;         // [n - 1] pair k re-detected (k_orb_out)
-  int* status;        // [2] converged, decision passes
+  int* status;        // [3] converged, decision passes, a level outgrew its room (orb_out_capacity)
 };
 constexpr int kCascadeMax = 8192;
 
@@ -1789,8 +1810,10 @@ struct LmTail {
 // the kind-1 / kind-2 launch on its own (a launch with no pairs)
 __global__ __launch_bounds__(256) void k_orb_tail(LmTail tl) {
   if (tl.kind == 1) orb_decide_body(tl.cs, tl.mode);
-  if (tl.kind == 2)
+  if (tl.kind == 2) {
     for (int k = threadIdx.x; k < tl.out.n_scans; k += 256) orb_out_at(tl.out, k);
+    orb_out_capacity(tl.out);
+  }
 }
 
 __device__ __forceinline__ void orb_lm_body(const PairArgs& p, int max_it, int pi) {
@@ -1854,8 +1877,10 @@ __global__ __launch_bounds__(kLmThreads) void k_orb_lm(PairArgs p, int max_it, L
   __shared__ int s_last;
   if (!wg_arrive_last(tl.arrive, (int)gridDim.x, &s_last)) return;  // every pair's stats and pose
   if (tl.kind == 1) orb_decide_body(tl.cs, tl.mode);
-  if (tl.kind == 2)
+  if (tl.kind == 2) {
     for (int k = threadIdx.x; k < tl.out.n_scans; k += 256) orb_out_at(tl.out, k);
+    orb_out_capacity(tl.out);
+  }
 }
 
 // A pair's distances and selection in one launch (the two kernels above, unchanged): the last of a
@@ -1904,6 +1929,13 @@ void features_per_level(int nfeatures, int* n) {
   n[kL - 1] = std::max(nfeatures - sum, 0);
 }
 
+// A level has room for lcap = 2 * n_l + 64 keypoints; retainBest keeps every response tied with the
+// n_l-th, so the reference has no such bound.  A scan whose level was cut (Args::ovf) fails its call.
+int capacity_fail(lislam_ctx* c, const char* who) {
+  return fail(c, LISLAM_ERR_CAPACITY, "%s: ORB level keypoint capacity exceeded (a level keeps at most 2 * n_l + 64 keypoints)",
+              who);
+}
+
 }  // namespace
 
 // One ORB engine: geometry, resize tables, mask pyramid, per-scan buffers for up to max_scans
@@ -1919,7 +1951,7 @@ struct OrbEngine {
   int xs = 0, ys = 0;
   uint8_t* mpyr = nullptr;
   uint8_t *pyr = nullptr, *blur = nullptr, *nms = nullptr, *desc = nullptr;
-  int *cand = nullptr, *lcnt = nullptr, *nkp = nullptr, *overflow = nullptr, *smap = nullptr;
+  int *cand = nullptr, *lcnt = nullptr, *nkp = nullptr, *ovf = nullptr, *smap = nullptr;
   float *cresp = nullptr, *lkp = nullptr, *kp = nullptr;
   float4* p3d = nullptr;
   ~OrbEngine() {
@@ -1941,7 +1973,7 @@ struct OrbEngine {
     a.S = max_scans;
     a.img = img; a.track = track;
     a.pyr = pyr; a.blur = blur; a.mpyr = mpyr; a.nms = nms; a.cand = cand; a.cresp = cresp;
-    a.lkp = lkp; a.lcnt = lcnt; a.kp = kp; a.p3d = p3d; a.desc = desc; a.nkp = nkp; a.overflow = overflow;
+    a.lkp = lkp; a.lcnt = lcnt; a.kp = kp; a.p3d = p3d; a.desc = desc; a.nkp = nkp; a.ovf = ovf;
     a.smap = nullptr;
     a.map_filter = map_filter;
     return a;
@@ -2069,9 +2101,9 @@ int engine_init(OrbEngine* e, lislam_ctx* c, int H, int W, int max_scans, int nf
   LISLAM_RC(e->alloc(&e->p3d, S * g.cap));
   LISLAM_RC(e->alloc(&e->desc, S * g.cap * 32));
   LISLAM_RC(e->alloc(&e->nkp, S));
-  LISLAM_RC(e->alloc(&e->overflow, 1));
+  LISLAM_RC(e->alloc(&e->ovf, S));
   LISLAM_RC(e->alloc(&e->smap, S));
-  LISLAM_HIPCHK(c, hipMemsetAsync(e->overflow, 0, 4, st));
+  LISLAM_HIPCHK(c, hipMemsetAsync(e->ovf, 0, S * 4, st));
   if (mask) {  // mask pyramid, once
     uint8_t* dmask = nullptr;
     LISLAM_RC(e->alloc(&dmask, (size_t)H * W));
@@ -2107,6 +2139,7 @@ Args args_slot(const OrbEngine* e, const uint8_t* img, const float4* track, int 
   a.p3d = e->p3d + s * g.cap;
   a.desc = e->desc + s * g.cap * 32;
   a.nkp = e->nkp + s;
+  a.ovf = e->ovf + s;
   return a;
 }
 
@@ -2329,12 +2362,13 @@ struct OrbBatch {
   // the device-decided re-detection cascade (k_orb_decide): state, lists, and its verdict copied
   // to pinned host memory; `pending` until a reader of the outputs has checked it
   CascadeArgs cs{};
-  int* h_status = nullptr;   // pinned [2]
+  int* h_status = nullptr;   // pinned [3]
   hipEvent_t settled = nullptr;
   bool pending = false;
   int pending_n = 0;
   int ran_n = 0;             // scans of the last lislam_batch_intensity_odometry (lislam_orb_batch_descriptors)
   int info[2] = {-1, 0};     // lislam_batch_orb_cascade_info
+  bool over = false;         // the last batch cut a level to its room: its outputs fail with LISLAM_ERR_CAPACITY
   ~OrbBatch() {
     if (side) (void)hipStreamSynchronize(side);
     if (side) destroy_stream(side);
@@ -2399,7 +2433,7 @@ int orb_batch_get(lislam_batch* b, int nfeatures, const uint8_t* mask, OrbBatch*
     int* qi = static_cast<int*>(q);
     cs.e2list = qi; cs.plist = qi + S; cs.redet = qi + 7 * S; cs.e2cnt = qi + 8 * S; cs.pcnt = qi + 8 * S + 2;
     cs.status = qi + 8 * S + 4;
-    LISLAM_HIPCHK(c, hipHostMalloc((void**)&ob->h_status, 2 * sizeof(int), hipHostMallocDefault));
+    LISLAM_HIPCHK(c, hipHostMalloc((void**)&ob->h_status, 3 * sizeof(int), hipHostMallocDefault));
     LISLAM_HIPCHK(c, hipEventCreateWithFlags(&ob->settled, hipEventDisableTiming));
   }
   *out = ob;
@@ -2479,7 +2513,13 @@ int batch_intensity_odometry(lislam_batch* b, OrbBatch* ob, int n_scans) {
   const OutArgs oa{ob->outS, ob->outT, ob->pb.stats, ob->pb.T, ob->pb.redet, ob->e1->nkp, n_scans};
   hipLaunchKernelGGL(k_orb_out, dim3(cdiv(n_scans, 256)), dim3(256), 0, st, oa);
   LISLAM_HIPCHK(c, hipGetLastError());
+  // the capacity flags of the n sets and of the 2n sets this batch detected
+  std::vector<int> o1(n_scans, 0), o2(n_scans, 0);
+  LISLAM_HIPCHK(c, hipMemcpyAsync(o1.data(), ob->e1->ovf, (size_t)n_scans * 4, hipMemcpyDeviceToHost, st));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(o2.data(), ob->e2->ovf, (size_t)n_scans * 4, hipMemcpyDeviceToHost, st));
   LISLAM_HIPCHK(c, hipStreamSynchronize(st));
+  ob->over = false;
+  for (int k = 0; k < n_scans; k++) ob->over |= o1[k] != 0 || (have2[k] && o2[k] != 0);
   return LISLAM_OK;
 }
 
@@ -2528,9 +2568,10 @@ int batch_intensity_odometry_dev(lislam_batch* b, OrbBatch* ob, int n_scans) {
   LISLAM_RC(engine_select_from(ob->e2, ob->e1, img, trk, cs.e2list, cs.e2cnt, n_scans));
   tl.kind = 2;
   tl.out = OutArgs{ob->outS, ob->outT, ob->pb.stats, ob->pb.T, cs.redet, ob->e1->nkp, n_scans};
+  tl.out.ovf1 = ob->e1->ovf; tl.out.ovf2 = ob->e2->ovf; tl.out.have2 = cs.have2; tl.out.over = cs.status + 2;
   LISLAM_RC(run_pairs(c, ob->e2, ob->e2, nullptr, nullptr, n_scans, 0.2, ob->pb, 0, true, nullptr, cs.plist, cs.pcnt, &tl));
   LISLAM_HIPCHK(c, hipGetLastError());
-  LISLAM_HIPCHK(c, hipMemcpyAsync(ob->h_status, cs.status, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(ob->h_status, cs.status, 3 * sizeof(int), hipMemcpyDeviceToHost, st));
   LISLAM_HIPCHK(c, hipEventRecord(ob->settled, st));
   ob->pending = true;
   ob->pending_n = n_scans;
@@ -2551,6 +2592,7 @@ int orb_settle(lislam_batch* b) {
   ob->pending = false;
   ob->info[0] = ob->h_status[0];
   ob->info[1] = ob->h_status[1];
+  ob->over = ob->h_status[2] != 0;  // came with the verdict; a redo below gathers its own
   if (ob->h_status[0] == 1) return LISLAM_OK;
   const hipStream_t main_stream = c->stream;
   const hipStream_t side = ob->st(c);
@@ -2584,6 +2626,7 @@ int lislam_batch_intensity_odometry(lislam_batch* b, int32_t n_scans, int32_t nf
   ob->pending = false;  // a newer batch replaces results nobody read
   ob->info[0] = -1;
   ob->info[1] = 0;
+  ob->over = false;
   const int rc = (n_scans < 2 || n_scans > kCascadeMax) ? batch_intensity_odometry(b, ob, n_scans)
                                                                                : batch_intensity_odometry_dev(b, ob, n_scans);
   c->stream = main_stream;
@@ -2592,6 +2635,8 @@ int lislam_batch_intensity_odometry(lislam_batch* b, int32_t n_scans, int32_t nf
     LISLAM_HIPCHK(c, hipStreamWaitEvent(main_stream, ob->done, 0));
   }
   ob->ran_n = rc == LISLAM_OK ? n_scans : 0;
+  // (the device cascade has not finished: its flag comes with its verdict, to whoever reads the outputs)
+  if (rc == LISLAM_OK && ob->over) return capacity_fail(c, "lislam_batch_intensity_odometry");
   return rc;
 }
 
@@ -2650,19 +2695,33 @@ int lislam_intensity_tracker_step(lislam_intensity_tracker* t, const uint8_t* im
   int h8[8] = {-1, 0, 0, 0, 0, 0, 0, 0};
   double T[7] = {0, 0, 0, 1, 0, 0, 0};
   bool cur2 = false;
+  // A frame one of whose levels outgrew its room fails the call (its flag comes with the copies the
+  // call waits for anyway) and is not kept: the tracker starts over with the next frame.
+  int over1 = 0, over2[2] = {0, 0};
+  auto dropped = [&]() {
+    t->have_prev = false;
+    t->prev2 = false;
+    return capacity_fail(c, "lislam_intensity_tracker_step");
+  };
   if (!t->have_prev) {
     LISLAM_HIPCHK(c, hipMemcpyAsync(&h8[2], t->e1.nkp + cs, 4, hipMemcpyDeviceToHost, st));
+    LISLAM_HIPCHK(c, hipMemcpyAsync(&over1, t->e1.ovf + cs, 4, hipMemcpyDeviceToHost, st));
     LISLAM_HIPCHK(c, hipStreamSynchronize(st));
+    if (over1) return dropped();
   } else {
     LISLAM_RC(run_pairs(c, &t->e1, t->prev2 ? &t->e2 : &t->e1, &cs, &ps, 1, 0.3, t->pb, 0, true));
     LISLAM_HIPCHK(c, hipMemcpyAsync(h8, t->pb.stats, 32, hipMemcpyDeviceToHost, st));
+    LISLAM_HIPCHK(c, hipMemcpyAsync(&over1, t->e1.ovf + cs, 4, hipMemcpyDeviceToHost, st));
     LISLAM_HIPCHK(c, hipStreamSynchronize(st));
+    if (over1) return dropped();
     if (h8[0] != 1) {  // re-detect both frames with 2 * nfeatures (intensity_feature_tracker.cpp:652-687)
       LISLAM_RC(engine_detect_slots(&t->e2, t->img, t->trk, cs, 1));
       if (!t->prev2) LISLAM_RC(engine_detect_slots(&t->e2, t->img, t->trk, ps, 1));
       LISLAM_RC(run_pairs(c, &t->e2, &t->e2, &cs, &ps, 1, 0.2, t->pb, 0, true));
       LISLAM_HIPCHK(c, hipMemcpyAsync(h8, t->pb.stats, 32, hipMemcpyDeviceToHost, st));
+      LISLAM_HIPCHK(c, hipMemcpyAsync(over2, t->e2.ovf, 8, hipMemcpyDeviceToHost, st));  // both slots' 2n sets
       LISLAM_HIPCHK(c, hipStreamSynchronize(st));
+      if (over2[0] || over2[1]) return dropped();
       h8[1] = 1;
       cur2 = true;
     }
@@ -2696,10 +2755,10 @@ static int orb_detect_impl(lislam_ctx* c, const uint8_t* image, const float* clo
   LISLAM_RC(engine_detect_slots(&e, dimg, dtrk, 0, 1));
   int cnt = 0, ovf = 0;
   LISLAM_HIPCHK(c, hipMemcpyAsync(&cnt, e.nkp, 4, hipMemcpyDeviceToHost, st));
-  LISLAM_HIPCHK(c, hipMemcpyAsync(&ovf, e.overflow, 4, hipMemcpyDeviceToHost, st));
+  LISLAM_HIPCHK(c, hipMemcpyAsync(&ovf, e.ovf, 4, hipMemcpyDeviceToHost, st));
   LISLAM_HIPCHK(c, hipStreamSynchronize(st));
   *n = cnt;
-  if (ovf) return fail(c, LISLAM_ERR_CAPACITY, "ORB level keypoint capacity exceeded");
+  if (ovf) return capacity_fail(c, map_filter ? "lislam_orb_detect_map" : "lislam_orb_detect");
   if (cnt > cap) return fail(c, LISLAM_ERR_CAPACITY, "lislam_orb_detect: %d keypoints > cap %d", cnt, cap);
   if (kp) LISLAM_HIPCHK(c, hipMemcpyAsync(kp, e.kp, (size_t)cnt * 24, hipMemcpyDefault, st));
   if (desc) LISLAM_HIPCHK(c, hipMemcpyAsync(desc, e.desc, (size_t)cnt * 32, hipMemcpyDefault, st));
@@ -2767,6 +2826,7 @@ int lislam_orb_batch_output(lislam_batch* b, int what, int scan, const void** sr
   OrbBatch* ob = static_cast<OrbBatch*>(b->orb);
   if (!ob) return LISLAM_ERR_STATE;
   LISLAM_RC(orb_settle(b));
+  if (ob->over) return capacity_fail(b->ctx, "lislam_batch_intensity_odometry");
   const Geom& g = ob->e1->g;
   switch (what) {
     case LISLAM_OUT_ORB_T: *src = ob->outT + (size_t)scan * 7; *cnt = 7; *esz = 8; return LISLAM_OK;
@@ -2794,6 +2854,7 @@ int lislam_orb_batch_descriptors(lislam_batch* b, const uint8_t** desc, const in
   OrbBatch* ob = static_cast<OrbBatch*>(b->orb);
   if (!ob || ob->ran_n == 0) return LISLAM_ERR_STATE;
   LISLAM_RC(orb_settle(b));
+  if (ob->over) return capacity_fail(b->ctx, "lislam_batch_intensity_odometry");
   *desc = ob->e1->desc;
   *counts = ob->e1->nkp;
   *cap = ob->e1->g.cap;
